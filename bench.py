@@ -15,9 +15,27 @@ token ids.  The prompts are first prefetched with the real chunked-prefill path
 whole batch: metadata prep, hipGraph replay of the 40-layer model (hand-written gfx950 kernels +
 hipBLASLt GEMMs), sampling, token feedback.  Nothing is skipped inside the timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (paged decode attention:
-~58% of the step's algorithmic bytes), timed live with HIP events on the launch stream;
-`cpu_baseline` is the oracle's torch-eager forward on this node's host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+figures (`value`, `ms_per_step`, p50 TTFT, the step's share of the HBM peak).  Its projection GEMMs run on the kernels
+recorded in bench_gemm_plans.json (tools/bench_plans.py: the engine's search and in-graph re-ranking, run once and kept as
+data), so every run of the same arguments launches the same kernels and computes the same bits; a shape without an
+entry, or $MSGL_GEMM_TUNE set, searches as the engine does.
+
+    --full               also everything that takes runs of its own or compares with a record: `roofline` of the
+                         dominant kernel (paged decode attention: ~58% of the step's algorithmic bytes, timed live
+                         with HIP events on the launch stream), the prefill-attention roofline, the latency regime
+                         (--small-batches), the end-to-end offline benchmark, `cpu_baseline` (the oracle's
+                         torch-eager forward on this node's host cores on a bounded sample), the metric's second
+                         configuration at --gpus 4, the records committed under profiles/, and the live GEMM search
+                         with its re-ranking inside the captured step and its report (`gemm_tune`)
+    --dump-outputs DIR   after the timed steps, write what the LAST timed step handed back as float32 .npy files:
+                         next_tokens.npy [batch] (the sampled token ids the caller of a decode step receives) and,
+                         with hipGraph on, logits.npy [batch, 16384] (the step's logits buffer the tokens were drawn
+                         from, at a fixed seeded sample of the vocabulary's columns, sorted: 16 MB).  Weights,
+                         prompts, page order and sampling are seeded and a plain run's kernels are recorded, so the
+                         same arguments give the same files.  (Under --full the kernels come from a timed search:
+                         where it settles on another split of K a sum is reordered, and at temperature 0.6 over a
+                         152 k-token vocabulary one changed last bit redraws the tokens after it.)
 """
 from __future__ import annotations
 
@@ -207,6 +225,110 @@ def measure_prefill_attention(device, hq: int, hkv: int, budget: int = 16384):
             "flops": c["flops"], "chunk_tokens": c["T"], "requests": c["B"]}
 
 
+def measure_decode_attention(engine, running, lens_now, model_name: str, page_size: int, world: int, device) -> dict:
+    """HBM roofline of the dominant kernel (paged decode attention + its merge kernel) at the contexts of the next step:
+    one layer's launch timed on its own with HIP events on the launch stream."""
+    from mini_sglang_amd import ops
+
+    be, B, it = engine.attn_backend, len(running), 2
+    hq, hkv, D = be.qo_heads, be.kv_heads, engine.cfg.model.head_dim
+    seq = torch.tensor(lens_now, dtype=torch.int32, device=device)
+    rows = torch.tensor([s.req.table_idx for s in running], dtype=torch.int32, device=device)
+    plan = torch.empty(be._plan_words, dtype=torch.int32, device=device)
+    ops.attn_decode_plan(plan, seq, B, be.max_bs, be.capacity, hq, hkv)
+    q = torch.randn((B, hq, D), device=device, dtype=torch.bfloat16)
+    o = torch.empty_like(q)
+    k_tok, v_tok = be._kv_tokens(0)
+    launch = lambda: ops.attn_decode(o, q, k_tok, v_tok, engine.page_table, rows, seq, plan, be._workspace, B,  # noqa: E731
+                                     be.max_bs, be.capacity, be.scale, slot_run=be.slot_run)
+    for _ in range(3):
+        launch()
+    # One layer's launch = attention kernel + merge kernel.  Three HIP-event readings on the launch stream:
+    #  * `us_per_launch` (what `achieved` / `frac` use): ONE event pair around 40 launches queued back to back, divided by
+    #    40 -- covers both kernels and the gaps between them, the stream never idles (as inside the captured step); this is
+    #    the figure rocprofv3 --kernel-trace reproduces as (attention + merge) average duration (+ ~0.3 us of gaps);
+    #  * `us_per_launch_event_gap_median` (round 5's headline, kept for comparison): an event after every launch, median
+    #    distance of consecutive events -- reads ~3 % LOW (an event's stamp is taken before the merge kernel has drained);
+    #  * `us_per_launch_idle_stream` (rounds 1-4): one synchronised event pair per launch -- adds the host-to-idle-GPU
+    #    launch latency to every sample (5-8 % high, box dependent).
+    reps, tot = 30, 0.0
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        e1.synchronize()
+        tot += e0.elapsed_time(e1)
+    attn_us_idle = tot * 1e3 / reps
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 4)]
+    for _ in range(3):
+        launch()
+    evs[0].record()
+    for i in range(reps + 3):
+        launch()
+        evs[i + 1].record()
+    evs[-1].synchronize()
+    gaps = sorted(x.elapsed_time(y) for x, y in zip(evs[3:-1], evs[4:]))  # the first three gaps = ramp of the queue
+    attn_us_gap = gaps[len(gaps) // 2] * 1e3
+    pair_reps, pair = 40, []
+    for _ in range(3):
+        for _ in range(5):
+            launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(pair_reps):
+            launch()
+        e1.record()
+        e1.synchronize()
+        pair.append(e0.elapsed_time(e1) * 1e3 / pair_reps)
+    attn_us = sorted(pair)[1]  # partial + merge kernels of one layer, median of three runs of 40
+    S = sum(lens_now)
+    attn_bytes = S * 2 * hkv * D * it + 2 * B * hq * D * it + S * 4 + 2 * B * 4  # SURVEY.md section 8d
+    achieved = attn_bytes / attn_us / 1e3
+    shape = f"{model_name} tp{world} B{B} page{page_size} bench_contexts"
+    traffic, traffic_src, traffic_ratio = pmc_traffic(attn_bytes, shape)
+    return {
+        "bound": "hbm", "kernel": "attn_decode_mfma_kernel + attn_decode_merge_kernel, one layer (both kernels timed)", "achieved": achieved,
+        "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+        "traffic_source": traffic_src, "traffic_over_algorithmic": traffic_ratio, "us_per_launch": attn_us,
+        "us_per_launch_event_gap_median": attn_us_gap, "us_per_launch_idle_stream": attn_us_idle,
+        "timing": "us_per_launch = one HIP-event pair around 40 launches (attention + merge each) queued back to back / 40, median of 3: covers both kernels; event_gap_median = round 5's method (reads ~3 % low); idle_stream = one synchronised pair per launch (rounds 1-4, reads 5-8 % high)",
+        "algorithmic_bytes": attn_bytes, "launch_shape": shape,
+    }
+
+
+PINNED_GEMM_PLANS = ROOT / "bench_gemm_plans.json"  # written by tools/bench_plans.py
+
+
+def pinned_gemm_plans(model_name: str, world: int, batch: int):
+    """The recorded projection-GEMM kernel choice of this decode shape (ops.export_gemm_plans data), or None: no entry for
+    the shape, or $MSGL_GEMM_TUNE asks for a search.  The engine's search is timed, and where two candidates are within
+    noise two processes settle on different kernels (seen: qkv at 36.7 vs 38.6 us, a 3-way against a 4-way split of K),
+    i.e. on different last bits -- which temperature-0.6 sampling over 152 k tokens turns into different tokens one step
+    later.  A plain run installs the recorded plans instead: the same kernels, hence the same outputs, every run."""
+    if "MSGL_GEMM_TUNE" in os.environ or not PINNED_GEMM_PLANS.exists():
+        return None
+    return json.loads(PINNED_GEMM_PLANS.read_text()).get(f"{model_name} tp{world} B{batch}")
+
+
+DUMP_LOGIT_COLUMNS = 16384  # of the vocabulary's columns, drawn once with a fixed seed: [256, 16384] fp32 = 16 MB
+
+
+def dump_outputs(out_dir: Path, step_output, logits) -> None:
+    """--dump-outputs: what the last timed decode step handed back.  `step_output` is the ForwardOutput of
+    OfflineRunner.decode_step (the sampled token per request); `logits` the graph runner's static logits buffer of the
+    same step ([batch, vocab], model dtype; None when the step ran eager and kept none)."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    step_output.copy_done_event.synchronize()
+    np.save(out_dir / "next_tokens.npy", step_output.next_tokens_cpu.numpy().astype(np.float32))  # ids < 2^24: exact
+    if logits is not None:
+        cols = np.sort(np.random.default_rng(0).choice(logits.shape[1], min(DUMP_LOGIT_COLUMNS, logits.shape[1]), replace=False))
+        sample = logits[:, torch.from_numpy(cols).to(logits.device)]
+        np.save(out_dir / "logits.npy", sample.float().cpu().numpy())
+
+
 def self_launch(gpus: int) -> int:
     """`python3 bench.py --gpus N` with no launcher around it: start the N ranks through torch.distributed.run (one
     process per GPU, loopback rendezvous on a free port) and hand back its exit code; rank 0's JSON line goes to this
@@ -341,10 +463,10 @@ def check_collectives(comm, rank: int, world: int, device) -> dict:
 
 def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, device, share_gpu: bool,
                  primary: bool) -> dict:
-    """One decode workload (chunked prefill, W + K decode steps, roofline of the attention launch) of `model_name` at
-    TP = world.  primary: the headline entry (with the latency regime, the prefill-attention roofline, the GEMM search
-    report); a secondary entry (Qwen3-32B at --gpus 4) carries the step time, TTFT and the collectives report only."""
-    from mini_sglang_amd import ops
+    """One decode workload (chunked prefill, W + K decode steps; --full: roofline of the attention launch) of `model_name`
+    at TP = world.  primary: the headline entry (with the GEMM search report; --full: the latency regime, the
+    prefill-attention roofline); a secondary entry (Qwen3-32B at --gpus 4) carries the step time, TTFT and the
+    collectives report only."""
     from mini_sglang_amd.core import SamplingParams
     from mini_sglang_amd.engine import Engine, EngineConfig
     from mini_sglang_amd.model import PRESETS
@@ -382,10 +504,11 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
     B = args.batch
     # the latency-regime section is a single-GPU extra: under TP every additional graph is another capture
     # with collectives inside, which the headline measurement does not need
-    small_batches = list(args.small_batches) if (world == 1 and primary) else []
+    small_batches = list(args.small_batches) if (world == 1 and primary and args.full) else []
     contexts = bench_contexts(B)
     use_graph = os.environ.get("MSGL_BENCH_NO_GRAPH", "0") != "1"
     max_seq = 4096  # max_seq_len_override of the reference bench
+    pinned = None if args.full else pinned_gemm_plans(model_name, world, B)
     ecfg = EngineConfig(model=mcfg, dtype=torch.bfloat16, tp_rank=rank, tp_size=world, max_running_req=B,
                         cuda_graph_bs=sorted(set([b for b in small_batches if b < B] + [B])) if use_graph else [],
                         page_size=args.page_size,
@@ -393,7 +516,11 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
                         # ranks sharing one GPU cannot each take 90 % of its memory: a fixed pool that holds the batch
                         num_page_override=(B * (max_seq // 2) // args.page_size) if share_gpu else None,
                         comm_split_tokens=int(os.environ.get("MSGL_BENCH_COMM_SPLIT", "2048")) if world > 1 else 0, tp_cpu_group=dist.group.WORLD if world > 1 else None,
-                        gemm_tune=os.environ.get("MSGL_GEMM_TUNE", "full"))
+                        # --full searches the library's solutions and the hand-written kernels and re-ranks the finalists inside
+                        # the captured step (~45 re-captures x 20 replays: 15 s at this shape); a plain run installs the plans
+                        # recorded from that procedure where the shape has an entry, and runs the search alone where not
+                        gemm_tune="off" if pinned else os.environ.get("MSGL_GEMM_TUNE", "full"),
+                        refine_in_graph=args.full)
     engine, err = None, None
     try:
         engine = Engine(ecfg, device)
@@ -419,6 +546,12 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
         ecfg.cuda_graph_bs = []
         use_graph = False
         engine = Engine(ecfg, device)
+    if pinned:
+        from mini_sglang_amd import ops
+
+        ops.import_gemm_plans(pinned, device.index or 0)
+        if use_graph:
+            engine.graph_runner.capture(B)  # the engine captured with the library's heuristic in force: again, with the plans
     runner = OfflineRunner(engine, max_extend_tokens=16384, seed=0)
 
     rnd = random.Random(1234)
@@ -459,7 +592,7 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        runner.decode_step(running)
+        last = runner.decode_step(running)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -469,68 +602,19 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
     ms_per_step = elapsed * 1e3 / args.steps
     tokens_per_s = B * args.steps / elapsed
 
-    # ---------------- roofline of the dominant kernel (paged decode attention) ----------------
+    if args.dump_outputs and rank == 0:  # before anything else replays the graph: its logits buffer is the last step's
+        dump_outputs(Path(args.dump_outputs), last, engine.graph_runner.logits[:B] if use_graph else None)
+
     lens_now = [s.req.device_len for s in running]  # contexts of the next step
     be = engine.attn_backend
     it = 2
     hq, hkv, D = be.qo_heads, be.kv_heads, mcfg.head_dim
-    seq = torch.tensor(lens_now, dtype=torch.int32, device=device)
-    rows = torch.tensor([s.req.table_idx for s in running], dtype=torch.int32, device=device)
-    plan = torch.empty(be._plan_words, dtype=torch.int32, device=device)
-    ops.attn_decode_plan(plan, seq, B, be.max_bs, be.capacity, hq, hkv)
-    q = torch.randn((B, hq, D), device=device, dtype=torch.bfloat16)
-    o = torch.empty_like(q)
-    k_tok, v_tok = be._kv_tokens(0)
-    launch = lambda: ops.attn_decode(o, q, k_tok, v_tok, engine.page_table, rows, seq, plan, be._workspace, B,  # noqa: E731
-                                     be.max_bs, be.capacity, be.scale, slot_run=be.slot_run)
-    for _ in range(3):
-        launch()
-    # One layer's launch = attention kernel + merge kernel.  Three HIP-event readings on the launch stream:
-    #  * `us_per_launch` (what `achieved` / `frac` use): ONE event pair around 40 launches queued back to back, divided by
-    #    40 -- covers both kernels and the gaps between them, the stream never idles (as inside the captured step); this is
-    #    the figure rocprofv3 --kernel-trace reproduces as (attention + merge) average duration (+ ~0.3 us of gaps);
-    #  * `us_per_launch_event_gap_median` (round 5's headline, kept for comparison): an event after every launch, median
-    #    distance of consecutive events -- reads ~3 % LOW (an event's stamp is taken before the merge kernel has drained);
-    #  * `us_per_launch_idle_stream` (rounds 1-4): one synchronised event pair per launch -- adds the host-to-idle-GPU
-    #    launch latency to every sample (5-8 % high, box dependent).
-    reps, tot = 30, 0.0
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-        e1.synchronize()
-        tot += e0.elapsed_time(e1)
-    attn_us_idle = tot * 1e3 / reps
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 4)]
-    for _ in range(3):
-        launch()
-    evs[0].record()
-    for i in range(reps + 3):
-        launch()
-        evs[i + 1].record()
-    evs[-1].synchronize()
-    gaps = sorted(x.elapsed_time(y) for x, y in zip(evs[3:-1], evs[4:]))  # the first three gaps = ramp of the queue
-    attn_us_gap = gaps[len(gaps) // 2] * 1e3
-    pair_reps, pair = 40, []
-    for _ in range(3):
-        for _ in range(5):
-            launch()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(pair_reps):
-            launch()
-        e1.record()
-        e1.synchronize()
-        pair.append(e0.elapsed_time(e1) * 1e3 / pair_reps)
-    attn_us = sorted(pair)[1]  # partial + merge kernels of one layer, median of three runs of 40
     S = sum(lens_now)
-    attn_bytes = S * 2 * hkv * D * it + 2 * B * hq * D * it + S * 4 + 2 * B * 4
-    achieved = attn_bytes / attn_us / 1e3
     # whole-step algorithmic bytes per rank: streamed weights + KV read/write + logits
     kv_tok = 2 * mcfg.num_layers * hkv * D * it
     step_bytes = engine.model.streamed_bytes_per_step() + (S + B) * kv_tok + B * mcfg.vocab_size * it
     step_gbps = step_bytes / (ms_per_step * 1e-3) / 1e9
+    roofline = measure_decode_attention(engine, running, lens_now, model_name, args.page_size, world, device) if args.full else None
 
     # ---------------- latency regime: the same model at small decode batches (not part of `value`) --------
     small = {}
@@ -552,10 +636,8 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
         sb = int(k_)
         sb_bytes = engine.model.streamed_bytes_per_step() + (sum(lens_now[:sb]) + sb) * kv_tok + sb * mcfg.vocab_size * it
         small_frac[k_] = round(sb_bytes / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-    shape = f"{model_name} tp{world} B{B} page{args.page_size} bench_contexts"
-    traffic, traffic_src, traffic_ratio = pmc_traffic(attn_bytes, shape)
     prefill_roofline = None
-    if rank == 0 and primary and not args.no_prefill_roofline:
+    if rank == 0 and primary and args.full and not args.no_prefill_roofline:
         try:
             prefill_roofline = measure_prefill_attention(device, hq, hkv)
         except Exception as e:  # never lose the headline numbers to the side measurement
@@ -578,17 +660,8 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
             "collectives": None if world == 1 else collectives["paths"],
         },
         "ttft_p50_ms": ttft_p50,
-        "small_batch_ms_per_step": small,
-        "small_batch_step_roofline_frac": small_frac,
-        "roofline": {
-            "bound": "hbm", "kernel": "attn_decode_mfma_kernel + attn_decode_merge_kernel, one layer (both kernels timed)", "achieved": achieved,
-            "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-            "traffic_source": traffic_src, "traffic_over_algorithmic": traffic_ratio, "us_per_launch": attn_us,
-            "us_per_launch_event_gap_median": attn_us_gap, "us_per_launch_idle_stream": attn_us_idle,
-            "timing": "us_per_launch = one HIP-event pair around 40 launches (attention + merge each) queued back to back / 40, median of 3: covers both kernels; event_gap_median = round 5's method (reads ~3 % low); idle_stream = one synchronised pair per launch (rounds 1-4, reads 5-8 % high)",
-            "algorithmic_bytes": attn_bytes, "launch_shape": shape,
-        },
-        "prefill_roofline": prefill_roofline,
+        **({"small_batch_ms_per_step": small, "small_batch_step_roofline_frac": small_frac, "roofline": roofline,
+            "prefill_roofline": prefill_roofline} if args.full else {}),
         "step_roofline": {
             "bound": "hbm", "bytes_per_step_per_rank": step_bytes, "achieved": step_gbps, "peak": HBM_PEAK_GBPS,
             "unit": "GB/s", "frac": step_gbps / HBM_PEAK_GBPS,
@@ -607,7 +680,7 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
         us = sum(r["best_us"] * (1 if r["name"] == "lm_head" else L) for r in full)
         result["step_roofline"]["gemm_weight_TBps"] = wbytes / us / 1e6
         result["step_roofline"]["gemm_ms_per_step_back_to_back"] = us / 1e3
-    if primary and world == 1:
+    if primary and world == 1 and args.full:
         ratio, src = gemm_traffic_over_algorithmic()
         # "committed": from the rocprofv3 PMC passes kept under profiles/ (counters cannot be read from inside this process)
         result["step_roofline"]["gemm_traffic_over_algorithmic"] = {"kind": "committed", "value": ratio, "source": src}
@@ -627,10 +700,12 @@ def run_workload(args, model_name: str, rank: int, local_rank: int, world: int, 
                                if r.get("silu_fused_us") else {})) for r in engine.gemm_report],
         }
         result["gemm_tune"]["refined_in_graph"] = getattr(engine, "refine_report", [])
+        if pinned:
+            result["gemm_tune"] = {"mode": "recorded plans", "source": PINNED_GEMM_PLANS.name, "kernels": pinned["kernels"]}
     else:
         result["gemm_plans_at_full_batch"] = {r["name"]: dict(us=round(r["best_us"], 1), kernel=r["kernel"][:70]) for r in full}
     engine.shutdown()  # raises if a peer-to-peer barrier ever timed out (NaN-poisoned collectives)
-    del runner, states, running, be, k_tok, v_tok, launch, engine, q, o
+    del runner, states, running, be, engine, last
     import gc
 
     gc.collect()
@@ -649,6 +724,12 @@ def main() -> None:
     ap.add_argument("--model", default="qwen3-14b")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--page-size", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements besides the headline (attention / prefill rooflines, small batches, end-to-end "
+                         "offline benchmark, CPU baseline, second configuration, committed records); the --no-* and "
+                         "--small-batches options below trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/next_tokens.npy and DIR/logits.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end README offline benchmark (extra keys)")
     ap.add_argument("--no-prefill", action="store_true", help="fill the KV pool with random data instead")
@@ -662,6 +743,8 @@ def main() -> None:
                          "(tools/rank_shard_bench.py): an upper bound on the TP = N speed-up before any link is paid")
     ap.add_argument("--tp1-ms", type=float, default=None, help="with --rank-shard: the TP1 ms/step to compare against")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.rank_shard > 1:
         from tools.rank_shard_bench import main as rank_shard_main
 
@@ -689,8 +772,6 @@ def main() -> None:
 
     import torch.distributed as dist
 
-    from mini_sglang_amd.model import PRESETS
-
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         # one node: rendezvous and the RCCL bootstrap over loopback (the box's hostname may not resolve);
@@ -713,6 +794,15 @@ def main() -> None:
     result["launch"] = ("self-launched: bench.py started its ranks through torch.distributed.run"
                         if os.environ.get("MSGL_BENCH_SELF_LAUNCHED") == "1" else
                         "external launcher (torchrun)" if world > 1 else "single process")
+    if args.full:
+        add_full_report(result, args, rank, local_rank, world, device, share_gpu)
+    print_result(result, rank, world)
+
+
+def add_full_report(result: dict, args, rank: int, local_rank: int, world: int, device, share_gpu: bool) -> None:
+    """--full: what the benchmark measures or looks up besides its headline workload."""
+    from mini_sglang_amd.model import PRESETS
+
     mcfg = PRESETS[args.model]
     contexts = bench_contexts(args.batch)
     ms_per_step = result["ms_per_step"]
@@ -802,14 +892,19 @@ def main() -> None:
             result["cpu_baseline"] = cpu_baseline(mcfg, result.pop("_lens_now", contexts))
         except Exception as e:  # never lose the GPU numbers to a host-side problem
             result["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+
+
+def print_result(result: dict, rank: int, world: int) -> None:
+    """Rank 0 prints the one JSON line; its `summary` repeats the main figures (null / empty for what only --full measures)."""
     result.pop("_lens_now", None)
     if rank == 0:
         # the LAST object of the line (a reader that keeps only the tail of stdout still sees the headline numbers)
         e2e = result.get("e2e_offline", {})
+        attn = result.get("roofline")
         result["summary"] = {
-            "ms_per_step": round(ms_per_step, 3), "tokens_per_s": round(result["value"]),
+            "ms_per_step": round(result["ms_per_step"], 3), "tokens_per_s": round(result["value"]),
             "step_frac_of_8TBps": round(result["step_roofline"]["frac"], 4),
-            "attn_decode_us": round(result["roofline"]["us_per_launch"], 1), "attn_decode_frac": round(result["roofline"]["frac"], 4),
+            "attn_decode_us": attn and round(attn["us_per_launch"], 1), "attn_decode_frac": attn and round(attn["frac"], 4),
             "small_batch_ms_per_step": result.get("small_batch_ms_per_step"),
             "ttft_p50_ms": result.get("ttft_p50_ms"),
             "e2e_offline_tok_s": {k: round(v["throughput_tok_s"]) for k, v in e2e.items() if "throughput_tok_s" in v},
@@ -823,6 +918,8 @@ def main() -> None:
         }
         print(json.dumps(result), flush=True)
     if world > 1:
+        import torch.distributed as dist
+
         dist.destroy_process_group()
 
 

@@ -172,6 +172,55 @@ def test_bench_self_launch_command_is_the_drivers_contract_line():
     assert env["MSGL_BENCH_SELF_LAUNCHED"] == "1" and env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_float32_tokens_and_a_fixed_logit_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's token ids and its logits at a seeded, sorted sample of the vocabulary's
+    columns, both float32, the same columns on every call, far below 64 MB at the bench's own shape."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    B, V = 5, 3 * bench.DUMP_LOGIT_COLUMNS + 17
+    tokens = torch.tensor([0, 7, V - 1, 151935, 3], dtype=torch.int32)
+    step = types.SimpleNamespace(next_tokens_cpu=tokens, copy_done_event=types.SimpleNamespace(synchronize=lambda: None))
+    logits = torch.arange(B * V, dtype=torch.float32).view(B, V).to(torch.bfloat16)
+    bench.dump_outputs(tmp_path / "a", step, logits)
+    bench.dump_outputs(tmp_path / "b", step, logits)
+    tok, lg = np.load(tmp_path / "a" / "next_tokens.npy"), np.load(tmp_path / "a" / "logits.npy")
+    assert tok.dtype == np.float32 and tok.tolist() == tokens.tolist()
+    assert lg.dtype == np.float32 and lg.shape == (B, bench.DUMP_LOGIT_COLUMNS)
+    assert np.array_equal(lg, np.load(tmp_path / "b" / "logits.npy"))
+    # row 0 of `logits` holds (the bf16 rounding of) its own column numbers: the sample is sorted, without repeats, in range
+    cols = np.sort(np.random.default_rng(0).choice(V, bench.DUMP_LOGIT_COLUMNS, replace=False))
+    assert np.all(np.diff(cols) > 0) and np.array_equal(lg[0], logits[0].float().numpy()[cols])
+    assert 256 * bench.DUMP_LOGIT_COLUMNS * 4 + 256 * 4 <= 64 * 1000 * 1000
+    bench.dump_outputs(tmp_path / "c", step, None)  # an eager step keeps no logits buffer: tokens only
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["next_tokens.npy"]
+
+
+def test_bench_default_shape_has_recorded_gemm_plans(monkeypatch):
+    """A plain bench.py run must launch the same projection kernels every time: its default shape has an entry in
+    bench_gemm_plans.json in the form ops.import_gemm_plans reads, one kernel named per projection; a shape without an
+    entry, or $MSGL_GEMM_TUNE set, leaves the choice to the engine's search."""
+    import ast
+
+    import bench
+    from mini_sglang_amd import ops
+
+    monkeypatch.delenv("MSGL_GEMM_TUNE", raising=False)
+    plans = bench.pinned_gemm_plans("qwen3-14b", 1, 256)
+    assert plans is not None and sorted(plans["kernels"]) == ["down", "gate_up", "lm_head", "o", "qkv"]
+    assert set(plans["tables"]) == set(ops._PLAN_TABLES)
+    keys = [ast.literal_eval(k) for t in plans["tables"].values() for k in t]
+    assert keys and all(len(k) == 7 and k[1] == 256 for k in keys)
+    assert all(len(row) == 9 and row[0] == 256 for row in plans["library"])
+    assert bench.pinned_gemm_plans("qwen3-14b", 4, 256) is None and bench.pinned_gemm_plans("qwen3-0.6b", 1, 256) is None
+    monkeypatch.setenv("MSGL_GEMM_TUNE", "full")
+    assert bench.pinned_gemm_plans("qwen3-14b", 1, 256) is None
+
+
 def test_p2p_error_word_decodes_to_a_message_on_both_sides():
     """csrc/comm_p2p.hip `Error word`: bits 0-3 = 1 + phase, 4-7 = collective kind, 8-15 = block, 16-19 = peer, bit 20 = the
     copy a failing rank wrote into a peer's header."""

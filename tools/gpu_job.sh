@@ -6,7 +6,7 @@
 #   kv_probe          tools/kv_stream_probe.hip (request shape x policy x landing place for the paged K/V stream)
 #   decode_ab:<impls> tools/decode_ab.py on the six shapes with the given select codes (comma-separated)
 #   tests:<expr>      pytest -m gpu -k <expr>          tests_all   the whole GPU suite
-#   bench             the driver's bench command       bench_fast  the same without e2e / cpu baseline / prefill roofline
+#   bench             bench.py --full                  bench_fast  the same without e2e / cpu baseline / prefill roofline
 #   trace_step        rocprofv3 kernel trace of the timed steps -> <tag>_bench_timed_steps_kernel_breakdown.txt
 #   rank_shard        bench.py --rank-shard on the five TP configurations
 #   trace_replay:<model>[:<requests>]  tools/trace_replay.py at the reference's six scales, --cache naive
@@ -38,7 +38,7 @@ for JOB in "$@"; do
     tests_all)
       ( time timeout 1700 python -m pytest tests -m gpu -q -x ) > gpurun_out/${TAG}_pytest.log 2>&1; tail -12 gpurun_out/${TAG}_pytest.log | cut -c1-300 ;;
     bench|bench_fast)
-      EXTRA=""; [ $NAME == bench_fast ] && EXTRA="--no-e2e --no-cpu-baseline --no-prefill-roofline"
+      EXTRA="--full"; [ $NAME == bench_fast ] && EXTRA="--full --no-e2e --no-cpu-baseline --no-prefill-roofline"
       ( time timeout 900 python bench.py --steps 20 --warmup 5 $EXTRA $ARG ) > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
       tail -3 gpurun_out/${TAG}_bench.err | cut -c1-300
       python - <<PY
