@@ -398,6 +398,32 @@ int msgl_ro_gemm_nt(void* out, const void* x, const void* w, int M, int N, int K
                     int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mixture-of-experts MLP (csrc/moe.hip), bf16 with fp32 accumulation.  Replaces: FusedMoe.forward with activation "silu"
+ * and apply_router_weight_on_input = False (P/moe/fused.py:230-256): fused_topk (sgl_kernel.topk_softmax),
+ * moe_align_block_size, the two grouped Triton GEMMs around silu_and_mul, moe_sum_reduce.
+ *   msgl_moe_route:  logits [T, E] contiguous (MSGL_BF16 / MSGL_F32) -> fp32 softmax over E, the k largest probabilities
+ *                    in descending order (ties: the lowest expert index first), w /= sum(w) + 1e-8 if renormalize;
+ *                    topk_weights fp32 [T, k], topk_ids int32 [T, k].  E <= 256, k <= min(8, E).
+ *   msgl_moe_forward: out[t] = sum over slots s = 0 .. k-1, in that order, of
+ *                        topk_weights[t, s] * (silu(x[t] . w1[e][:I_l]^T) * (x[t] . w1[e][I_l:]^T)) . w2[e]^T,  e = topk_ids[t, s]
+ *                    x [T, hidden], w1 [E, 2 I_l, hidden] ([gate; up] row order), w2 [E, hidden, I_l], out [T, hidden], all
+ *                    contiguous bf16.  hidden % 64 == 0, I_l % 32 == 0, E <= 256, k <= min(8, E), T >= 1 (at most 65535
+ *                    64-row work items per call: min(E, T k) + T k / 64).  A slot whose id is outside [0, E) adds nothing.
+ *                    Every launch's grid is a function of the arguments only (the routing is read on the device), nothing
+ *                    is allocated, no float atomics: bit-repeatable, and a token's row does not depend on the other tokens.
+ *                    out may alias x.
+ *   msgl_moe_workspace_bytes: scratch of msgl_moe_forward (256-byte aligned) for the same arguments: the pair list sorted
+ *                    by expert with every expert padded to 16 rows, the work-item tables, act [pairs, I_l] bf16 and the
+ *                    per-pair fp32 partial outputs.  Negative (MSGL_EINVAL) outside the shape contract.
+ * ---------------------------------------------------------------------- */
+int msgl_moe_route(float* topk_weights, int32_t* topk_ids, const void* logits, int T, int E, int k, int renormalize,
+                   int logits_dtype, void* stream);
+int64_t msgl_moe_workspace_bytes(int T, int E, int k, int hidden, int I_l);
+int msgl_moe_forward(const void* x, const void* w1, const void* w2, const float* topk_weights, const int32_t* topk_ids,
+                     void* workspace, int64_t workspace_bytes, void* out, int T, int E, int k, int hidden, int I_l,
+                     void* stream);
+
+/* ------------------------------------------------------------------------
  * Native radix prefix tree (libmsgl_hip.so, csrc/radix.cpp; host code, no device work).
  * Replaces: the tree walk of RadixPrefixCache -- _tree_walk, RadixTreeNode.split_at / get_match_len, lock_handle,
  * evict, _collect_leave_nodes_for_evict (python/minisgl/kvcache/radix_cache.py:65-77, 111-130, 147-175, 189-230),

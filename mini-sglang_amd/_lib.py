@@ -106,6 +106,9 @@ HIP_SIGNATURES = {
     "msgl_ro_gemm_max_units": (_i, [_i]),
     "msgl_ro_gemm_workspace_bytes": (_l, [_i, _i, _i]),
     "msgl_ro_gemm_nt": (_i, [_p, _p, _p, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _p, _l, _p]),
+    "msgl_moe_route": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "msgl_moe_workspace_bytes": (_l, [_i, _i, _i, _i, _i]),
+    "msgl_moe_forward": (_i, [_p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
 }
 
 COMM_SIGNATURES = {

@@ -41,6 +41,7 @@ HIP_SOURCES = [
     "gemm_m256.hip",
     "gemm_g3.hip",
     "gemm_ro.hip",
+    "moe.hip",
     "comm_p2p.hip",
 ]
 COMM_SOURCES = ["comm.cpp"]

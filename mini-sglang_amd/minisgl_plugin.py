@@ -672,6 +672,30 @@ def _install_vectorized_glue() -> None:
         setattr(sched, name, fn)
 
 
+class HipMoeBackend:
+    """MoE backend "hip" (moe_backend="hip" / --moe-backend hip): FusedMoe.forward (P/moe/fused.py:230-256) on
+    csrc/moe.hip.  Like the reference's, the result is written into `hidden_states` and that tensor is returned.
+    Registered as a virtual subclass of BaseMoeBackend by install() (minisgl is not importable before it)."""
+
+    def forward(self, hidden_states, w1, w2, gating_output, topk: int, renormalize: bool, activation: str = "silu",
+                apply_router_weight_on_input: bool = False):
+        from . import ops
+
+        if activation != "silu" or apply_router_weight_on_input:
+            raise ValueError(f"HipMoeBackend: only SiLU experts with the router weight on the output are implemented "
+                             f"(activation={activation!r}, apply_router_weight_on_input={apply_router_weight_on_input})")
+        return ops.fused_moe(hidden_states, w1, w2, gating_output.contiguous(), topk, renormalize, out=hidden_states)
+
+
+def _install_moe_backend() -> None:
+    """SUPPORTED_MOE_BACKENDS.register("hip") (P/moe/__init__.py:16-27); the reference's "auto" keeps choosing "fused"."""
+    from minisgl.moe import SUPPORTED_MOE_BACKENDS, BaseMoeBackend
+
+    BaseMoeBackend.register(HipMoeBackend)
+    if "hip" not in SUPPORTED_MOE_BACKENDS.supported_names():
+        SUPPORTED_MOE_BACKENDS.register("hip")(HipMoeBackend)
+
+
 def gemm_report() -> List[dict]:
     """What the last pre-capture search chose (one dict per (batch size, projection))."""
     return list(_STATE["gemm_report"])
@@ -724,6 +748,7 @@ def install(stub_zmq: bool = True, *, fast_linear: bool = True, fused_attention:
 
             return HipAttnBackend(config, ctx=get_global_ctx(), tp_size=get_tp_info().size)
 
+    _install_moe_backend()
     _STATE["gemm_tune"] = gemm_tune or os.environ.get("MSGL_GEMM_TUNE", "heuristic")
     if fast_linear:
         _install_fast_linear()

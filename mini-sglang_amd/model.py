@@ -56,6 +56,11 @@ class ModelConfig:
     tie_word_embeddings: bool = False
     qk_norm: bool = True  # Qwen3: per-head RMSNorm on q and k (P/models/qwen3.py:21)
     name: str = "custom"
+    # mixture of experts (P/models/config.py; Qwen3-MoE): num_experts > 0 replaces every layer's dense MLP
+    num_experts: int = 0
+    num_experts_per_tok: int = 0
+    moe_intermediate_size: int = 0
+    norm_topk_prob: bool = True
 
 
 PRESETS: Dict[str, ModelConfig] = {
@@ -75,6 +80,11 @@ PRESETS: Dict[str, ModelConfig] = {
     # Qwen3-14B's layer at full width (every projection has the real decode shapes, so the searched plans are the real ones),
     # two layers and a 32 k vocabulary: 2 GB of weights -- small enough to write as a checkpoint in a test
     "qwen3-14b-width-2l": ModelConfig(2, 40, 8, 128, 5120, 32768, 17408, max_position=4096, name="Qwen3-14B width, 2 layers"),
+    # mixture of experts: 128 experts, top-8, no dense MLP (intermediate_size is the config's unused dense value)
+    "qwen3-30b-a3b": ModelConfig(48, 32, 4, 128, 2048, 151936, 6144, name="Qwen3-30B-A3B", num_experts=128,
+                                 num_experts_per_tok=8, moe_intermediate_size=768),
+    "tiny-moe": ModelConfig(2, 10, 2, 128, 256, 1024, 512, max_position=4096, name="tiny-moe", num_experts=8,
+                            num_experts_per_tok=2, moe_intermediate_size=96),
 }
 
 
@@ -86,9 +96,13 @@ class LayerWeights:
     k_norm: Optional[torch.Tensor]
     o: torch.Tensor         # [hidden, Hq_l * D]               row-parallel
     post_norm: torch.Tensor
-    gate_up: torch.Tensor   # [2 * I_l, hidden]                (P/layers/linear.py:56-71); rows in
+    gate_up: Optional[torch.Tensor]  # [2 * I_l, hidden]       (P/layers/linear.py:56-71); rows in
                             # ops.interleave_gate_up order when DenseDecoder.gate_up_ilv
-    down: torch.Tensor      # [hidden, I_l]                    row-parallel
+    down: Optional[torch.Tensor]     # [hidden, I_l]           row-parallel
+    # mixture-of-experts layers (gate_up / down are None): P/layers/moe.py:33-43, experts sharded on the intermediate dim
+    router: Optional[torch.Tensor] = None  # [E, hidden]           replicated
+    w1: Optional[torch.Tensor] = None      # [E, 2 * I_l, hidden]  [gate; up] rows per expert
+    w2: Optional[torch.Tensor] = None      # [E, hidden, I_l]
 
 
 def vocab_shard(vocab_size: int, tp_size: int, tp_rank: int):
@@ -174,16 +188,23 @@ class DenseDecoder:
             return torch.ones(n, device=device, dtype=dtype)
 
         H = cfg.hidden_size
+        self.moe = cfg.num_experts > 0
+        self.moe_inter = heads_per_rank(cfg.moe_intermediate_size, tp_size) if self.moe else 0
         self.embed = w(self.vocab_tp, H)
         self.layers: List[LayerWeights] = []
         for _ in range(cfg.num_layers):
-            self.layers.append(LayerWeights(
-                input_norm=ones(H), qkv=w(self.q_dim + 2 * self.kv_dim, H),
-                q_norm=ones(D) if cfg.qk_norm else None, k_norm=ones(D) if cfg.qk_norm else None,
-                o=w(H, self.q_dim), post_norm=ones(H), gate_up=w(2 * self.inter, H), down=w(H, self.inter)))
+            attn = dict(input_norm=ones(H), qkv=w(self.q_dim + 2 * self.kv_dim, H),
+                        q_norm=ones(D) if cfg.qk_norm else None, k_norm=ones(D) if cfg.qk_norm else None,
+                        o=w(H, self.q_dim), post_norm=ones(H))
+            if self.moe:
+                E = cfg.num_experts
+                self.layers.append(LayerWeights(**attn, gate_up=None, down=None, router=w(E, H),
+                                                w1=w(E, 2 * self.moe_inter, H), w2=w(E, H, self.moe_inter)))
+            else:
+                self.layers.append(LayerWeights(**attn, gate_up=w(2 * self.inter, H), down=w(H, self.inter)))
         # gate_up rows in the block-32 interleaved order the fused projection + SiLU.mul epilogue needs (csrc/gemm_g3.hip);
         # every consumer goes through ops.linear_silu, the oracle gets the reference layout back (gate_up_reference)
-        self.gate_up_ilv = bool(fused and _FUSE_SILU and device.type == "cuda" and self.inter % 64 == 0)
+        self.gate_up_ilv = bool(fused and _FUSE_SILU and device.type == "cuda" and self.inter % 64 == 0 and not self.moe)
         if self.gate_up_ilv:
             idx = ops.gate_up_interleave_index(self.inter, device)
             for lw in self.layers:
@@ -197,15 +218,21 @@ class DenseDecoder:
         if not self.cfg.tie_word_embeddings:
             n += self.lm_head.numel()
         for lw in self.layers:
-            n += sum(t.numel() for t in (lw.input_norm, lw.qkv, lw.o, lw.post_norm, lw.gate_up, lw.down))
+            mlp = (lw.router, lw.w1, lw.w2) if self.moe else (lw.gate_up, lw.down)
+            n += sum(t.numel() for t in (lw.input_norm, lw.qkv, lw.o, lw.post_norm) + mlp)
             n += 0 if lw.q_norm is None else lw.q_norm.numel() + lw.k_norm.numel()
         return n * self.embed.element_size()
 
-    def streamed_bytes_per_step(self) -> int:
-        """Weight bytes a decode step must read: everything but the embedding table (gathered rows only)."""
+    def streamed_bytes_per_step(self, tokens: Optional[int] = None) -> int:
+        """Weight bytes a decode step must read: everything but the embedding table (gathered rows only).  Expert
+        layers: a step of `tokens` rows touches at most min(E, tokens * k) experts per layer, the bound counted here
+        (the routing decides the real number); without `tokens`, every expert."""
         b = self.weight_bytes()
         if not self.cfg.tie_word_embeddings:
             b -= self.embed.numel() * self.embed.element_size()
+        if self.moe and tokens is not None:
+            idle = self.cfg.num_experts - min(self.cfg.num_experts, tokens * self.cfg.num_experts_per_tok)
+            b -= sum(idle * (lw.w1[0].numel() + lw.w2[0].numel()) for lw in self.layers) * self.embed.element_size()
         return b
 
     # ------------------------------------------------------------------ weights from a checkpoint
@@ -243,6 +270,13 @@ class DenseDecoder:
                 put(lw.q_norm, state[p + "self_attn.q_norm.weight"])
                 put(lw.k_norm, state[p + "self_attn.k_norm.weight"])
             put(lw.o, state[p + "self_attn.o_proj.weight"].chunk(n, dim=1)[r])
+            if self.moe:  # P/models/weight.py:63-119: experts stacked on a new dim 0, each sharded like a dense gated MLP
+                ex = [p + f"mlp.experts.{e}." for e in range(cfg.num_experts)]
+                put(lw.router, state[p + "mlp.gate.weight"])
+                put(lw.w1, torch.stack([torch.cat([col(state[q + "gate_proj.weight"]), col(state[q + "up_proj.weight"])], dim=0)
+                                        for q in ex]))
+                put(lw.w2, torch.stack([state[q + "down_proj.weight"].chunk(n, dim=1)[r] for q in ex]))
+                continue
             gu = torch.cat([col(state[p + "mlp.gate_proj.weight"]), col(state[p + "mlp.up_proj.weight"])], dim=0)
             put(lw.gate_up, gu.index_select(0, ops.gate_up_interleave_index(self.inter, gu.device)) if self.gate_up_ilv
                 else gu)
@@ -267,6 +301,9 @@ class DenseDecoder:
         fold = self.fused and self.tp_size == 1 and _ROWSTREAM_FUSE
         norm = {"fold": "norm"} if fold else {}
         act = {"fold": "act_interleaved" if self.gate_up_ilv else "act"} if fold else {}
+        if self.moe:  # the expert MLP is ops.fused_moe: no gate_up / down projection to plan
+            return [("qkv", [l.qkv for l in pick], self.cfg.hidden_size), ("o", [l.o for l in pick], self.q_dim),
+                    ("lm_head", [self.lm_head], self.cfg.hidden_size)]
         return [("qkv", [l.qkv for l in pick], self.cfg.hidden_size, norm), ("o", [l.o for l in pick], self.q_dim),
                 ("gate_up", [l.gate_up for l in pick], self.cfg.hidden_size, {"silu_interleaved": self.gate_up_ilv, **norm}),
                 ("down", [l.down for l in pick], self.inter, act), ("lm_head", [self.lm_head], self.cfg.hidden_size, norm)]
@@ -344,7 +381,7 @@ class DenseDecoder:
         # Measured inside the captured step (tools/small_batch_ab.py, profiles/r04_small_batch_ab.json): folding the norms is
         # worth 0.13 / 0.07-0.11 ms per step at one / two rows and nothing at four; SiLU.mul pays at one row only.
         T = x.shape[0]
-        rs_on = _ROWSTREAM_FUSE and self.fused and self.tp_size == 1 and T <= ops.ROWSTREAM_FOLD_NORM_MAX_M
+        rs_on = _ROWSTREAM_FUSE and self.fused and self.tp_size == 1 and T <= ops.ROWSTREAM_FOLD_NORM_MAX_M and not self.moe
         pending: Optional[torch.Tensor] = None
         spare: Optional[torch.Tensor] = None
 
@@ -391,6 +428,15 @@ class DenseDecoder:
             # down_proj feeds the NEXT layer's input norm (or the final norm): its all-reduce / slab reduce joins that norm
             last = li + 1 == len(self.layers)
             nxt = self.final_norm if last else self.layers[li + 1].input_norm
+            if self.moe:  # P/models/utils.py MoEMLP: router projection, expert MLP, all-reduce; then the next add + norm
+                x = self.row_parallel_norm(o.view(-1, self.q_dim), lw.o, residual, lw.post_norm)
+                x = ops.fused_moe(x, lw.w1, lw.w2, ops.linear(x, lw.router), cfg.num_experts_per_tok, cfg.norm_topk_prob)
+                if self.tp_size > 1:
+                    x = self.comm.all_reduce_add_rmsnorm(x, residual, nxt, cfg.rms_norm_eps)
+                else:
+                    fi.fused_add_rmsnorm(x, residual, nxt, cfg.rms_norm_eps)
+                normed_ahead = True
+                continue
             d_gu = ops.rowstream_planned(T, lw.gate_up, ops.ROWSTREAM_ADD_NORM) if rs_on else None
             act_mode = ops.ROWSTREAM_SILU_INTERLEAVED if self.gate_up_ilv else ops.ROWSTREAM_SILU
             # SiLU.mul in the staging pass pays at one row only (M = 4: 43 vs 39 us for the pair, profiles/r04_rowstream_bench.json)

@@ -1379,3 +1379,80 @@ def gemm_tune(x: torch.Tensor, weights, out: Optional[torch.Tensor] = None, max_
     return dict(M=M, N=N, K=K, best_us=best.value, default_us=default.value, index=idx.value, split_k=split.value,
                 tried=tried.value,
                 kernel=buf.value.decode(errors="replace"))
+
+
+# ---------------------------------------------------------------------------- mixture of experts (csrc/moe.hip)
+MOE_MAX_CHUNK_TOKENS = 32768  # per msgl_moe_forward call; the GEMM workspace usually sets a lower limit
+
+
+def _moe_route_into(weights: torch.Tensor, ids: torch.Tensor, logits: torch.Tensor, k: int, renormalize: bool) -> None:
+    check(
+        lib().msgl_moe_route(weights.data_ptr(), ids.data_ptr(), logits.data_ptr(), logits.shape[0], logits.shape[1], k,
+                             int(bool(renormalize)), _logits_dt(logits), _stream()),
+        "moe_route",
+    )
+
+
+def moe_route(logits: torch.Tensor, k: int, renormalize: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fused_topk of the reference (P/moe/fused.py:9-28): fp32 softmax over the experts, the k largest probabilities in
+    descending order (ties: lowest expert index), optionally renormalised -> (weights fp32 [T, k], ids int32 [T, k])."""
+    _need_cuda(logits)
+    assert logits.dim() == 2 and logits.is_contiguous(), "router logits must be a contiguous [T, E] tensor"
+    T = logits.shape[0]
+    weights = torch.empty((T, k), dtype=torch.float32, device=logits.device)
+    ids = torch.empty((T, k), dtype=torch.int32, device=logits.device)
+    if T:
+        _moe_route_into(weights, ids, logits, k, renormalize)
+    return weights, ids
+
+
+def moe_workspace_bytes(T: int, E: int, k: int, hidden: int, inter: int) -> int:
+    n = lib().msgl_moe_workspace_bytes(T, E, k, hidden, inter)
+    check(int(n), "moe_workspace_bytes")
+    return int(n)
+
+
+def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits: torch.Tensor, topk: int,
+              renormalize: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The expert MLP of FusedMoe.forward (P/moe/fused.py:230-256; SiLU experts, router weight on the output):
+    x [T, hidden], w1 [E, 2 I, hidden] ([gate; up] rows), w2 [E, hidden, I], router_logits [T, E] -> [T, hidden].
+    Routing tables, activations and per-pair partial sums live in the GEMM workspace (nothing is allocated per call but
+    `out`, every grid is fixed by the shapes: capturable); a batch whose scratch would not fit runs as token chunks,
+    which changes no bit, a token's row being independent of the rest of the batch -- but every chunk streams the
+    touched experts' weights again (Qwen3-30B-A3B: about 1024 tokens per chunk, the fp32 partials being 64 KiB per
+    token).  `out` may be `x`."""
+    _need_cuda(x, w1, w2, router_logits)
+    assert x.dim() == 2 and w1.dim() == 3 and w2.dim() == 3 and router_logits.dim() == 2
+    assert x.dtype == w1.dtype == w2.dtype == torch.bfloat16, "fused_moe: bf16 activations and expert weights only"
+    assert x.is_contiguous() and w1.is_contiguous() and w2.is_contiguous() and router_logits.is_contiguous()
+    T, hidden = x.shape
+    E, inter = w2.shape[0], w2.shape[2]
+    assert w1.shape == (E, 2 * inter, hidden) and w2.shape == (E, hidden, inter) and router_logits.shape == (T, E)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous() and out.is_cuda
+    if T == 0:
+        return out
+    _no_pending_slabs(x.device)
+    ws = gemm_workspace(x.device)
+    chunk = min(T, MOE_MAX_CHUNK_TOKENS)
+    while True:  # routing results (256-byte aligned) sit in front of the kernels' own scratch
+        route_bytes = 2 * ((chunk * topk * 4 + 255) // 256 * 256)
+        need = moe_workspace_bytes(chunk, E, topk, hidden, inter)
+        if route_bytes + need <= ws.numel() or chunk == 1:
+            break
+        chunk = (chunk + 1) // 2
+    base = ws.data_ptr()
+    assert base % 256 == 0
+    for t0 in range(0, T, chunk):
+        n = min(chunk, T - t0)
+        weights = ws[:n * topk * 4].view(torch.float32).view(n, topk)
+        ids = ws[route_bytes // 2:route_bytes // 2 + n * topk * 4].view(torch.int32).view(n, topk)
+        _moe_route_into(weights, ids, router_logits[t0:t0 + n], topk, renormalize)
+        check(
+            lib().msgl_moe_forward(x[t0:t0 + n].data_ptr(), w1.data_ptr(), w2.data_ptr(), weights.data_ptr(), ids.data_ptr(),
+                                   base + route_bytes, ws.numel() - route_bytes, out[t0:t0 + n].data_ptr(), n, E, topk, hidden,
+                                   inter, _stream()),
+            "moe_forward",
+        )
+    return out
