@@ -424,6 +424,20 @@ int msgl_moe_forward(const void* x, const void* w1, const void* w2, const float*
                      void* stream);
 
 /* ------------------------------------------------------------------------
+ * The same expert MLP for prefill-sized batches (csrc/moe_tall.hip): items of up to 256 rows, both GEMM operands staged
+ * through LDS, a three-launch multi-workgroup align, and the down projection + slot sum run per column slab of `hidden`.
+ *   msgl_moe_forward_tall: the arguments, shape contract and conventions of msgl_moe_forward, and BIT-IDENTICAL output
+ *                    (at most 65535 256-row work items per call: min(E, T k) + T k / 256).  The slab width W is the
+ *                    largest multiple of 128 columns whose fp32 partials [T k, W] fit workspace_bytes behind the tables
+ *                    and act (all of hidden if that fits): grids depend on the shapes and workspace_bytes only.
+ *   msgl_moe_workspace_bytes_tall: the minimum scratch, at W = 128.  Negative (MSGL_EINVAL) outside the shape contract.
+ * ---------------------------------------------------------------------- */
+int64_t msgl_moe_workspace_bytes_tall(int T, int E, int k, int hidden, int I_l);
+int msgl_moe_forward_tall(const void* x, const void* w1, const void* w2, const float* topk_weights, const int32_t* topk_ids,
+                          void* workspace, int64_t workspace_bytes, void* out, int T, int E, int k, int hidden, int I_l,
+                          void* stream);
+
+/* ------------------------------------------------------------------------
  * Native radix prefix tree (libmsgl_hip.so, csrc/radix.cpp; host code, no device work).
  * Replaces: the tree walk of RadixPrefixCache -- _tree_walk, RadixTreeNode.split_at / get_match_len, lock_handle,
  * evict, _collect_leave_nodes_for_evict (python/minisgl/kvcache/radix_cache.py:65-77, 111-130, 147-175, 189-230),

@@ -109,6 +109,8 @@ HIP_SIGNATURES = {
     "msgl_moe_route": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "msgl_moe_workspace_bytes": (_l, [_i, _i, _i, _i, _i]),
     "msgl_moe_forward": (_i, [_p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
+    "msgl_moe_workspace_bytes_tall": (_l, [_i, _i, _i, _i, _i]),
+    "msgl_moe_forward_tall": (_i, [_p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
 }
 
 COMM_SIGNATURES = {

@@ -42,6 +42,7 @@ HIP_SOURCES = [
     "gemm_g3.hip",
     "gemm_ro.hip",
     "moe.hip",
+    "moe_tall.hip",
     "comm_p2p.hip",
 ]
 COMM_SOURCES = ["comm.cpp"]

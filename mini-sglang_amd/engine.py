@@ -267,6 +267,10 @@ class Engine:
         self.model = DenseDecoder(cfg.model, dtype=cfg.dtype, device=self.device, tp_rank=cfg.tp_rank,
                                   tp_size=cfg.tp_size, seed=cfg.seed, comm=comm, fused=cfg.fused_qkv_path,
                                   comm_split_tokens=cfg.comm_split_tokens, comm_overlap=overlap)
+        if self.model.moe:  # the tall expert path's scratch counts as model memory, not as room for KV pages
+            m = cfg.model
+            ops.moe_reserve(self.device, cfg.prefill_tokens or 8192, m.num_experts, m.num_experts_per_tok, m.hidden_size,
+                            self.model.moe_inter)
         torch.cuda.synchronize(self.device)
         free_after = self._agreed_free_memory(torch.cuda.mem_get_info(self.device)[0])
 

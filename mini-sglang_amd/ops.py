@@ -1412,15 +1412,77 @@ def moe_workspace_bytes(T: int, E: int, k: int, hidden: int, inter: int) -> int:
     return int(n)
 
 
+# The tall path (csrc/moe_tall.hip) keeps its scratch in a buffer of its own, one per device, grown on demand up to
+# MOE_WORKSPACE_MAX_BYTES: Qwen3-30B-A3B at 8192 tokens needs 103 MB of act, which leaves room for two column slabs.
+_MOE_WS: dict = {}
+MOE_WORKSPACE_MAX_BYTES = 512 << 20
+# auto dispatch: the tall path where the MEAN run of an expert, T k / E pairs, reaches this many rows (shapes only, never
+# the routing).  Measured with tools/moe_bench.py on Qwen3-30B-A3B: T = 1024 (64 pairs per expert) is the smallest batch where
+# the tall path wins by more than the 2 % box-to-box noise; at 512 the rows path is still ahead.
+MOE_TALL_MIN_PAIRS_PER_EXPERT = 64
+
+
+def moe_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
+    """The tall path's scratch buffer of `device`, at least min(nbytes, MOE_WORKSPACE_MAX_BYTES) bytes -- except during
+    stream capture, where it never grows: the caller gets what exists, or the GEMM workspace if nothing does."""
+    key = torch.device(device).index or 0
+    ws = _MOE_WS.get(key)
+    want = min(int(nbytes), MOE_WORKSPACE_MAX_BYTES)
+    if ws is not None and ws.numel() >= want:
+        return ws
+    if torch.cuda.is_current_stream_capturing():
+        return ws if ws is not None else gemm_workspace(device)
+    _MOE_WS[key] = ws = torch.empty(want, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _moe_route_bytes(T: int, k: int) -> int:
+    return 2 * ((T * k * 4 + 255) // 256 * 256)
+
+
+@functools.lru_cache(maxsize=4096)
+def moe_workspace_bytes_tall(T: int, E: int, k: int, hidden: int, inter: int) -> int:
+    """The least scratch fused_moe(impl="tall") needs for T tokens in one call: the routing results plus
+    msgl_moe_workspace_bytes_tall (tables, act and fp32 partials of one 128-column slab)."""
+    n = lib().msgl_moe_workspace_bytes_tall(T, E, k, hidden, inter)
+    check(int(n), "moe_workspace_bytes_tall")
+    return _moe_route_bytes(T, k) + int(n)
+
+
+def moe_reserve(device: torch.device, T: int, E: int, k: int, hidden: int, inter: int) -> torch.Tensor:
+    """Grow the tall path's buffer to what T tokens want with all of `hidden` as one slab (capped at the maximum)."""
+    full = moe_workspace_bytes_tall(T, E, k, hidden, inter) + T * k * 4 * max(hidden - 128, 0)
+    return moe_workspace(device, full)
+
+
+def _moe_tall_chunk(T: int, E: int, k: int, hidden: int, inter: int, nbytes: int) -> int:
+    """The most tokens (<= T) whose scratch fits nbytes at the narrowest slab; the need grows with the token count."""
+    if moe_workspace_bytes_tall(T, E, k, hidden, inter) <= nbytes:
+        return T
+    lo, hi = 0, T  # lo fits (0 = nothing does), hi does not
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if moe_workspace_bytes_tall(mid, E, k, hidden, inter) <= nbytes:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
 def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits: torch.Tensor, topk: int,
-              renormalize: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              renormalize: bool, out: Optional[torch.Tensor] = None, impl: Optional[str] = None) -> torch.Tensor:
     """The expert MLP of FusedMoe.forward (P/moe/fused.py:230-256; SiLU experts, router weight on the output):
     x [T, hidden], w1 [E, 2 I, hidden] ([gate; up] rows), w2 [E, hidden, I], router_logits [T, E] -> [T, hidden].
-    Routing tables, activations and per-pair partial sums live in the GEMM workspace (nothing is allocated per call but
-    `out`, every grid is fixed by the shapes: capturable); a batch whose scratch would not fit runs as token chunks,
-    which changes no bit, a token's row being independent of the rest of the batch -- but every chunk streams the
-    touched experts' weights again (Qwen3-30B-A3B: about 1024 tokens per chunk, the fp32 partials being 64 KiB per
-    token).  `out` may be `x`."""
+    impl "rows": csrc/moe.hip, 64-row items, built for decode.  Routing tables, activations and per-pair partial sums
+    live in the GEMM workspace (nothing is allocated per call but `out`, every grid is fixed by the shapes: capturable); a
+    batch whose scratch would not fit runs as token chunks, which changes no bit, a token's row being independent of the
+    rest of the batch -- but every chunk streams the touched experts' weights again (Qwen3-30B-A3B: about 1024 tokens
+    per chunk, the fp32 partials being 64 KiB per token).
+    impl "tall": csrc/moe_tall.hip, 256-row items for prefill, the same bits.  Scratch comes from moe_workspace(); the
+    down projection runs per column slab of `hidden`, as wide as the buffer allows, and only a batch that does not fit
+    at 128 columns runs as token chunks.
+    impl None: "tall" where T k >= MOE_TALL_MIN_PAIRS_PER_EXPERT E, else "rows".  `out` may be `x`."""
+    assert impl in (None, "rows", "tall"), f"fused_moe: impl must be None, 'rows' or 'tall', not {impl!r}"
     _need_cuda(x, w1, w2, router_logits)
     assert x.dim() == 2 and w1.dim() == 3 and w2.dim() == 3 and router_logits.dim() == 2
     assert x.dtype == w1.dtype == w2.dtype == torch.bfloat16, "fused_moe: bf16 activations and expert weights only"
@@ -1434,6 +1496,28 @@ def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits
     if T == 0:
         return out
     _no_pending_slabs(x.device)
+    if impl is None:
+        impl = "tall" if T * topk >= MOE_TALL_MIN_PAIRS_PER_EXPERT * E else "rows"
+    if impl == "tall":
+        ws = moe_reserve(x.device, min(T, MOE_MAX_CHUNK_TOKENS), E, topk, hidden, inter)
+        limit = min(ws.numel(), MOE_WORKSPACE_MAX_BYTES)
+        chunk = _moe_tall_chunk(min(T, MOE_MAX_CHUNK_TOKENS), E, topk, hidden, inter, limit)
+        if chunk == 0:
+            raise RuntimeError(f"fused_moe: {limit} bytes of scratch do not hold one token of the tall path")
+        route_bytes, base = _moe_route_bytes(chunk, topk), ws.data_ptr()
+        assert base % 256 == 0
+        for t0 in range(0, T, chunk):
+            n = min(chunk, T - t0)
+            weights = ws[:n * topk * 4].view(torch.float32).view(n, topk)
+            ids = ws[route_bytes // 2:route_bytes // 2 + n * topk * 4].view(torch.int32).view(n, topk)
+            _moe_route_into(weights, ids, router_logits[t0:t0 + n], topk, renormalize)
+            check(
+                lib().msgl_moe_forward_tall(x[t0:t0 + n].data_ptr(), w1.data_ptr(), w2.data_ptr(), weights.data_ptr(),
+                                            ids.data_ptr(), base + route_bytes, limit - route_bytes,
+                                            out[t0:t0 + n].data_ptr(), n, E, topk, hidden, inter, _stream()),
+                "moe_forward_tall",
+            )
+        return out
     ws = gemm_workspace(x.device)
     chunk = min(T, MOE_MAX_CHUNK_TOKENS)
     while True:  # routing results (256-byte aligned) sit in front of the kernels' own scratch

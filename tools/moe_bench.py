@@ -1,7 +1,9 @@
 """One layer's expert MLP at Qwen3-30B-A3B dimensions: ops.fused_moe (csrc/moe.hip) against a per-expert torch loop.
 
-    python tools/moe_bench.py [--out profiles/moe_bench.json] [--tokens 1,16,64,256,8192]
+    python tools/moe_bench.py [--out profiles/moe_bench.json] [--tokens 1,16,64,256,...,8192] [--impl both|rows|tall]
 
+`--impl both` times fused_moe(impl="rows") (csrc/moe.hip) at every T and impl="tall" (csrc/moe_tall.hip) at T >= 256, in this
+one process, and checks that the two outputs are the same bits; hip_us is the time of the implementation impl=None picks.
 HIP path: `--replays` calls inside one captured graph, rotating over `--layers` weight sets (a decode batch's touched
 experts would otherwise be served from the Infinity Cache), device events around the replay, median of `--rounds`.
 Baseline, same process and box: index_select -> F.linear -> silu * mul -> F.linear -> index_add_ per expert.  The routing
@@ -26,6 +28,7 @@ from mini_sglang_amd import ops  # noqa: E402
 from mini_sglang_amd.model import PRESETS  # noqa: E402
 
 PEAK_BYTES_PER_S = 8e12
+PEAK_BF16_FLOPS = 2.5e15
 
 
 def timed_us(fn, rounds: int, per_call: int) -> float:
@@ -62,7 +65,8 @@ def torch_loop(x, w1, w2, groups, out):
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / "moe_bench.json"))
-    ap.add_argument("--tokens", default="1,16,64,256,8192")
+    ap.add_argument("--tokens", default="1,16,64,256,512,1024,2048,4096,8192")
+    ap.add_argument("--impl", default="both", choices=["both", "rows", "tall"])
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=9)
@@ -81,16 +85,22 @@ def main() -> None:
     for T in [int(t) for t in args.tokens.split(",")]:
         x, logits, out = rnd(T, H, std=1.0), rnd(T, E, std=1.0), torch.empty((T, H), dtype=torch.bfloat16, device=dev)
         replays = args.replays if T <= 256 else 4
-        for w1, w2 in sets:  # warm-up: every shape and weight set of the timed window
-            ops.fused_moe(x, w1, w2, logits, k, cfg.norm_topk_prob, out=out)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for i in range(replays):
-                ops.fused_moe(x, *sets[i % len(sets)], logits, k, cfg.norm_topk_prob, out=out)
-        graph.replay()
-        hip_us = timed_us(graph.replay, args.rounds, replays)
-        hip_out = out.clone()
+        auto = "tall" if T * k >= ops.MOE_TALL_MIN_PAIRS_PER_EXPERT * E else "rows"
+        impls = [i for i in ("rows", "tall") if args.impl in (i, "both") and (i == "rows" or T >= 256 or args.impl == "tall")]
+        us, outs = {}, {}
+        for impl in impls:
+            for w1, w2 in sets:  # warm-up: every shape and weight set of the timed window
+                ops.fused_moe(x, w1, w2, logits, k, cfg.norm_topk_prob, out=out, impl=impl)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for i in range(replays):
+                    ops.fused_moe(x, *sets[i % len(sets)], logits, k, cfg.norm_topk_prob, out=out, impl=impl)
+            graph.replay()
+            us[impl] = timed_us(graph.replay, args.rounds, replays)
+            outs[impl] = out.clone()
+            del graph
+        hip_us, hip_out = us.get(auto, us[impls[0]]), outs.get(auto, outs[impls[0]])
 
         weights, ids = ops.moe_route(logits, k, cfg.norm_topk_prob)
         groups, state = expert_groups(weights, ids), {"i": 0}
@@ -105,7 +115,11 @@ def main() -> None:
         diff = (hip_out.float() - out.float()).abs().max().item() / out.float().abs().max().item()
         touched = int(ids.unique().numel())
         nbytes = touched * 3 * I * H * 2 + 2 * T * H * 2
-        rows.append(dict(T=T, experts_touched=touched, hip_us=round(hip_us, 2), torch_loop_us=round(torch_us, 2),
+        flops = 6 * T * k * I * H
+        both = dict(tall_over_rows=round(us["rows"] / us["tall"], 3), tall_equals_rows=bool(torch.equal(outs["rows"], outs["tall"])),
+                    tall_fraction_of_bf16_peak=round(flops / (us["tall"] * 1e-6) / PEAK_BF16_FLOPS, 4)) if len(us) == 2 else {}
+        rows.append(dict(T=T, experts_touched=touched, auto_impl=auto, **{f"{i}_us": round(v, 2) for i, v in us.items()}, **both,
+                         hip_us=round(hip_us, 2), torch_loop_us=round(torch_us, 2),
                          speedup=round(torch_us / hip_us, 2), algorithmic_bytes=nbytes,
                          hip_bytes_per_s=round(nbytes / (hip_us * 1e-6)), torch_loop_bytes_per_s=round(nbytes / (torch_us * 1e-6)),
                          hip_fraction_of_8TBps=round(nbytes / (hip_us * 1e-6) / PEAK_BYTES_PER_S, 4),
