@@ -176,6 +176,13 @@ int msgl_gelu_and_mul(void* out, const void* x, int64_t num_tokens, int64_t d, i
  * Both are capture-safe; grids are fixed by (max_bs, capacity, head counts).
  * min_chunk: smallest slot in tokens (power of two >= 16).  The plan buffer
  * must be 16-byte aligned; plan[0] = pieces, [1] = tokens per slot, [3] = slots.
+ *
+ * head_dim: 128 or 64, anything else is refused.  The plan does not depend on
+ * head_dim; the workspace keeps its layout with D = head_dim.  head_dim 64
+ * (csrc/attn_d64.hip) has ONE kernel -- 32-token steps on the matrix cores for
+ * both page-table forms, bf16 / fp16, any GQA group 1 .. 16 -- followed by its
+ * merge kernel; it runs under msgl_attn_decode_select code 0 (or 71) only, and
+ * msgl_attn_decode returns MSGL_EINVAL for head_dim 64 under any other code.
  * ---------------------------------------------------------------------- */
 /* Combining the split-KV partial sums: a merge kernel follows the partial kernel.  Alternative kept for measurement
  * (msgl_attn_decode_select(72)): the piece of a request that arrives LAST (per-(request, kv head) arrival counters at the end
@@ -228,6 +235,10 @@ int msgl_attn_decode_trace(void* stamps);
  * request b attends keys 0..seq_lens[b]-1 through the page table; query j of
  * q_len sees keys t <= seq_lens[b] - q_len + j (bottom-right causal mask).
  * tile_cu [B+1]: exclusive prefix of ceil(q_len_b / msgl_attn_prefill_q_tile(impl)).
+ * head_dim: 128 or 64, anything else is refused.  head_dim 64 (csrc/attn_d64.hip)
+ * has the DMA-staged kernel only: impl 0 / 4 select it, impl 2 with head_dim 64
+ * returns MSGL_EINVAL; q tiles are 128 rows and tile_cu / total_tiles /
+ * tile_order mean the same for both head dims.
  * ---------------------------------------------------------------------- */
 #define MSGL_PREFILL_QTILE 128
 int msgl_attn_prefill(void* out, const void* q, const void* k_cache, const void* v_cache,

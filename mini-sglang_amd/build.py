@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "norm_rope_act.hip",
     "attn_decode.hip",
     "attn_prefill.hip",
+    "attn_d64.hip",
     "sampling.hip",
     "gemm_skinny.hip",
     "gemm_rowstream.hip",

@@ -30,6 +30,7 @@
 
 #include <type_traits>
 
+#include "attn_params.h"
 #include "common.h"
 
 namespace msgl {
@@ -59,33 +60,7 @@ typedef __attribute__((address_space(4))) int CInt;                             
 typedef int I16a __attribute__((ext_vector_type(16), aligned(16)));
 typedef __attribute__((address_space(4))) I16a CI16;
 
-constexpr int kPlanHdr = 4;  // [0] n_items [1] tokens per slot [2] batch [3] n_slots
 constexpr float kNegBig = -3.0e38f;
-
-// plan buffer layout (int32 words):
-//   hdr[4] | item_start[max_bs] | n_chunks[max_bs] | tile_start[max_bs] | slot_first[capacity + 1] |
-//   items[4 * capacity] = (request, first tile, end tile, slot) |
-//   items2[4 * capacity] = (seq_len, pieces of the request, its first piece, 0) | arrivals[max_bs * kTicketHeads]
-// items2 repeats per piece what the kernels otherwise fetch by request AFTER the piece record arrived: with it a piece's
-// scalars are two independent loads at an address known from the piece number alone (and are prefetched for piece i + 1
-// while piece i streams).
-// arrivals[b][kv head]: how many pieces of request b have published their partial sums in the running launch (matrix-core
-// kernel under select code 72: the piece that arrives last combines them).  Zeroed by the plan kernel, left at zero by
-// every launch.
-constexpr int kTicketHeads = 64;
-__host__ __device__ inline int64_t plan_off_item_start() { return kPlanHdr; }
-__host__ __device__ inline int64_t plan_off_n_chunks(int max_bs) { return kPlanHdr + (int64_t)max_bs; }
-__host__ __device__ inline int64_t plan_off_tile_start(int max_bs) { return kPlanHdr + 2ll * max_bs; }
-__host__ __device__ inline int64_t plan_off_slot_first(int max_bs) { return kPlanHdr + 3ll * max_bs; }
-__host__ __device__ inline int64_t plan_off_items(int max_bs, int capacity) {
-  return ((kPlanHdr + 3ll * max_bs + capacity + 1 + 3) / 4) * 4;  // int4-aligned
-}
-__host__ __device__ inline int64_t plan_off_items2(int max_bs, int capacity) {
-  return plan_off_items(max_bs, capacity) + 4ll * capacity;
-}
-__host__ __device__ inline int64_t plan_off_arrivals(int max_bs, int capacity) {
-  return plan_off_items2(max_bs, capacity) + 4ll * capacity;
-}
 
 // ------------------------------------------------------------------------------
 // plan: seq_lens -> balanced slots.  One block, 256 threads.
@@ -193,25 +168,6 @@ __global__ __launch_bounds__(256) void decode_plan_kernel(int* __restrict__ plan
 // ------------------------------------------------------------------------------
 // partial attention
 // ------------------------------------------------------------------------------
-struct DecodeParams {
-  const uint16_t* q;
-  const uint16_t* k;
-  const uint16_t* v;
-  const int* page_table;
-  const int* req_rows;
-  const int* seq_lens;
-  const int* plan;
-  uint16_t* out;
-  float* part_o;
-  float* part_ml;
-  int64_t pt_stride, q_stride, kv_stride_tok, kv_stride_head, out_stride;
-  int max_bs, capacity, hq, hv, group;  // hv = virtual kv heads (hq / G), group = hq / real kv heads
-  int slot_run;               // aligned runs of this many positions map to consecutive slots (1: none)
-  float scale_log2;
-  unsigned long long* trace;  // diagnosis (msgl_attn_decode_trace): 16 clock stamps per wave, else nullptr
-  int* arrivals;              // plan_off_arrivals: per (request, kv head) arrival counters of the matrix-core kernel
-};
-
 struct Tile {
   V4 k[4], v[4];
 };
@@ -1299,7 +1255,10 @@ extern "C" int msgl_attn_decode(void* out, const void* q, const void* k_cache, c
   MSGL_REQUIRE(slot_run >= 1 && (slot_run & (slot_run - 1)) == 0, "attn_decode: slot_run %d must be a power of two",
                slot_run);
   MSGL_REQUIRE(batch >= 1 && batch <= max_bs && capacity >= max_bs, "attn_decode: bad batch/capacity");
-  MSGL_REQUIRE(head_dim == 128, "attn_decode: head_dim %d unsupported (128 only)", head_dim);
+  MSGL_REQUIRE(head_dim == 128 || head_dim == 64, "attn_decode: head_dim %d unsupported (64 and 128 only)", head_dim);
+  // head_dim 64 has one production kernel (csrc/attn_d64.hip): the diagnosis / A-B codes name head_dim 128 kernels only
+  MSGL_REQUIRE(head_dim == 128 || decode_impl() == 0 || decode_impl() == 71,
+               "attn_decode: head_dim 64 runs under select code 0 (or 71) only, not %d", decode_impl());
   MSGL_REQUIRE(num_kv_heads >= 1 && num_q_heads % num_kv_heads == 0, "attn_decode: %d q heads / %d kv heads",
                num_q_heads, num_kv_heads);
   MSGL_REQUIRE(pt_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(page_table) & 15u) == 0,
@@ -1339,6 +1298,12 @@ extern "C" int msgl_attn_decode(void* out, const void* q, const void* k_cache, c
   p.arrivals = const_cast<int*>(plan) + plan_off_arrivals(max_bs, capacity);
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc;
+  if (head_dim == 64) {  // same plan, same slots: the wave count msgl_attn_decode_plan sized the slots for
+    rc = launch_decode_d64(p, batch, (int64_t)decode_target_slots(G, p.hv, capacity, max_bs) * p.hv, dtype, s);
+    if (rc != MSGL_OK) return rc;
+    MSGL_CHECK_LAUNCH("attn_decode");
+    return MSGL_OK;
+  }
   if (dtype == MSGL_BF16) rc = dispatch_group<BF16>(G, p, batch, capacity, s);
   else if (dtype == MSGL_FP16) rc = dispatch_group<FP16>(G, p, batch, capacity, s);
   else {

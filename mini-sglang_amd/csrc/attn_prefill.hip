@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "attn_params.h"
 #include "common.h"
 
 namespace msgl {
@@ -51,68 +52,6 @@ __device__ __forceinline__ f32x16 mfma32(const U4& a, const U4& b, f32x16 c) {
   } else {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
                                                   0, 0, 0);
-  }
-}
-
-struct PrefillParams {
-  const uint16_t* q;
-  const uint16_t* k;
-  const uint16_t* v;
-  const int* page_table;
-  const int* req_rows;
-  const int* seq_lens;
-  const int* cu_q;
-  const int* tile_cu;
-  const int* tile_order;  // optional [total_tiles]: launch order of the q tiles (heaviest first); tr kernel only
-  uint16_t* out;
-  int64_t pt_stride, q_stride, kv_stride_tok, kv_stride_head, out_stride;
-  int batch, hq, group;
-  float scale_log2;
-};
-
-// element offset of a pool slot: slot and the token stride are both < 2^32 (checked at launch), so ONE v_mad_u64_u32
-// does it; the int64 x int64 product the types ask for costs two quarter-rate 32-bit multiplies and a carry chain more
-__device__ __forceinline__ int64_t slot_offset(int slot, int64_t stride_tok) {
-  return (int64_t)((uint64_t)(uint32_t)slot * (uint64_t)(uint32_t)stride_tok);
-}
-
-// The request a q tile belongs to and its scalars, in ONE memory latency for batches up to 64 requests (the bisection over
-// tile_cu followed by the four scalar loads paid log2(B) + 1 dependent ones: ~2.5 us of a workgroup that computes for
-// ~5 us on the benchmark's prefill chunks).  Lane i of a 64-request block loads request i's tile_cu, cu_q, cu_q[+1],
-// seq_len and table row together; b = the last request with tile_cu[b] <= tile is counted with a ballot and its values are
-// taken from that lane.
-struct TileRequest {
-  int b, q_begin, q_end, k_len, row, tile_first;
-};
-__device__ __forceinline__ TileRequest find_request(const PrefillParams& p, int tile, int lane) {
-  TileRequest r;
-  int base = 0;
-  for (;;) {
-    const int idx = min(base + lane, p.batch - 1);
-    const int tc = base + lane < p.batch ? p.tile_cu[idx] : 0x7fffffff;
-    const int cq0 = p.cu_q[idx], cq1 = p.cu_q[idx + 1], kl = p.seq_lens[idx];
-    const int rr = p.req_rows ? p.req_rows[idx] : idx;
-    const int cnt = __popcll(__ballot(tc <= tile));
-    if (cnt > 0 && (cnt < 64 || base + 64 >= p.batch)) {
-      const int l = cnt - 1;
-      r.b = base + l;
-      r.tile_first = __builtin_amdgcn_readlane(tc, l);
-      r.q_begin = __builtin_amdgcn_readlane(cq0, l);
-      r.q_end = __builtin_amdgcn_readlane(cq1, l);
-      r.k_len = __builtin_amdgcn_readlane(kl, l);
-      r.row = __builtin_amdgcn_readlane(rr, l);
-      return r;
-    }
-    if (cnt == 0) {  // the last request of the previous block (more than 64 requests only)
-      r.b = base - 1;
-      r.tile_first = p.tile_cu[r.b];
-      r.q_begin = p.cu_q[r.b];
-      r.q_end = p.cu_q[r.b + 1];
-      r.k_len = p.seq_lens[r.b];
-      r.row = p.req_rows ? p.req_rows[r.b] : r.b;
-      return r;
-    }
-    base += 64;
   }
 }
 
@@ -700,7 +639,9 @@ extern "C" int msgl_attn_prefill(void* out, const void* q, const void* k_cache, 
   if (batch == 0 || total_tiles == 0) return MSGL_OK;
   MSGL_REQUIRE(out && q && k_cache && v_cache && page_table && seq_lens && cu_seqlens_q && tile_cu,
                "attn_prefill: null pointer");
-  MSGL_REQUIRE(head_dim == 128, "attn_prefill: head_dim %d unsupported (128 only)", head_dim);
+  MSGL_REQUIRE(head_dim == 128 || head_dim == 64, "attn_prefill: head_dim %d unsupported (64 and 128 only)", head_dim);
+  MSGL_REQUIRE(head_dim == 128 || impl == 0 || impl == 4,
+               "attn_prefill: head_dim 64 has the DMA-staged kernel only (impl 0 = 4), not impl %d", impl);
   MSGL_REQUIRE(num_kv_heads >= 1 && num_q_heads % num_kv_heads == 0 && num_q_heads <= 65535,
                "attn_prefill: %d q heads / %d kv heads", num_q_heads, num_kv_heads);
   MSGL_REQUIRE(kv_stride_tok > 0 && kv_stride_tok < (1ll << 32), "attn_prefill: kv token stride %lld", (long long)kv_stride_tok);
@@ -738,6 +679,12 @@ extern "C" int msgl_attn_prefill(void* out, const void* q, const void* k_cache, 
   if (impl == 0) impl = 4;  // the DMA-staged kernel; impl 2 keeps its predecessor callable (A/B timing, cross-check in tests)
   const int64_t total = (int64_t)total_tiles * num_q_heads;
   MSGL_REQUIRE(total < (1ll << 30), "attn_prefill: %lld workgroups", (long long)total);
+  if (head_dim == 64) {  // csrc/attn_d64.hip
+    const int rc = launch_prefill_d64(p, total_tiles, dtype, s);
+    if (rc != MSGL_OK) return rc;
+    MSGL_CHECK_LAUNCH("attn_prefill");
+    return MSGL_OK;
+  }
   const unsigned blocks = (unsigned)((total + 7) / 8) * 8;  // 8 XCDs x n_per
   if (impl == 4) {
     if (dtype == MSGL_BF16) attn_prefill_dma_kernel<BF16><<<dim3(blocks), dim3(256), 0, s>>>(p, total_tiles);

@@ -73,6 +73,14 @@ PRESETS: Dict[str, ModelConfig] = {
         rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
                           original_max_position_embeddings=8192),
         qk_norm=False, name="Llama-3.1-70B-Instruct"),
+    # head_dim 64 (csrc/attn_d64.hip)
+    "llama-3.2-1b": ModelConfig(
+        16, 32, 8, 64, 2048, 128256, 8192, rms_norm_eps=1e-5, rope_base=500000.0, max_position=131072,
+        rope_scaling=dict(rope_type="llama3", factor=32.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                          original_max_position_embeddings=8192),
+        tie_word_embeddings=True, qk_norm=False, name="Llama-3.2-1B"),
+    "tiny-d64": ModelConfig(2, 8, 2, 64, 256, 1024, 512, rms_norm_eps=1e-5, qk_norm=False, max_position=4096,
+                            name="tiny-d64"),
     # small shapes for tests (same structure, GQA group 5 like Qwen3-14B)
     "tiny": ModelConfig(2, 10, 2, 128, 256, 1024, 512, max_position=4096, name="tiny"),
     "tiny-llama": ModelConfig(2, 8, 2, 128, 256, 1024, 512, rms_norm_eps=1e-5, qk_norm=False, max_position=4096,
