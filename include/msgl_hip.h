@@ -46,7 +46,7 @@ extern "C" {
 /* dtype codes for logits */
 #define MSGL_F32 2
 
-#define MSGL_ABI_VERSION 5
+#define MSGL_ABI_VERSION 6
 
 /* Last error message of the calling thread ("" if none). */
 const char* msgl_last_error(void);
@@ -407,6 +407,27 @@ int64_t msgl_ro_gemm_workspace_bytes(int M, int N, int slices);
 int msgl_ro_gemm_nt(void* out, const void* x, const void* w, int M, int N, int K, int64_t ldx, int64_t ldw,
                     int64_t ldo, int dtype, int tiles, int slices, int flags, void* workspace,
                     int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * W8A16 projection GEMM (csrc/gemm_w8.hip): block-scaled OCP e4m3 weights as the published FP8 checkpoints store them
+ * (`weight` float8_e4m3fn [N, K] + `weight_scale_inv` fp32 [N/128, K/128]), bf16 activations, fp32 accumulation.
+ *   msgl_w8_gemm_nt:  out[m, n] = round_bf16( sum_b s[n/128, b] * sum_{k in block b} x[m, k] * float(q[n, k]) )
+ *                    1 <= M <= 256, N % 128 == 0, K % 128 == 0; x [M, K] bf16 (dtype must be MSGL_BF16), q [N, K] bytes,
+ *                    scales [N/128, K/128] contiguous fp32, out [M, N] bf16; ldx % 8 == 0, ldq % 16 == 0, ldo % 4 == 0,
+ *                    x / q 16-byte and out 8-byte aligned.  The fp8 value is converted exactly and the scale multiplies
+ *                    the block's fp32 partial sum.  One launch reads every weight byte from HBM once, whatever M is.
+ *                    Knobs (results do not depend on them beyond fp32 summation order): `slices` = waves splitting K
+ *                    inside a workgroup, summed in LDS in slice order; `row_tiles` (1, 2, 4) = waves of a workgroup on
+ *                    different weight rows sharing the staged activations; slices * row_tiles <= 8, slices <= K/128, and
+ *                    the staged chunk ((M rounded up to 16) * slices * 256 bytes) as well as the slice sums must fit
+ *                    64 KB of LDS.  Deterministic, no atomics, no workspace, capturable; the grid depends on the
+ *                    arguments only.
+ *   msgl_w8_dequant:  out[n, k] = round_bf16(float(q[n, k]) * s[n/128, k/128]) (product in fp32), out [N, K] bf16 with
+ *                    ldo % 8 == 0, 16-byte aligned: the 16-bit GEMM paths then serve batches above 256 rows.
+ * ---------------------------------------------------------------------- */
+int msgl_w8_gemm_nt(void* out, const void* x, const void* q, const float* scales, int M, int N, int K, int64_t ldx,
+                    int64_t ldq, int64_t ldo, int dtype, int slices, int row_tiles, void* stream);
+int msgl_w8_dequant(void* out, const void* q, const float* scales, int N, int K, int64_t ldq, int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------
  * Mixture-of-experts MLP (csrc/moe.hip), bf16 with fp32 accumulation.  Replaces: FusedMoe.forward with activation "silu"

@@ -42,6 +42,7 @@ HIP_SOURCES = [
     "gemm_m256.hip",
     "gemm_g3.hip",
     "gemm_ro.hip",
+    "gemm_w8.hip",
     "moe.hip",
     "moe_tall.hip",
     "comm_p2p.hip",

@@ -123,6 +123,7 @@ class EngineConfig:
     gemm_tune: str = "heuristic"  # "off" | "heuristic" | "full": library solution search per graph batch size
     refine_in_graph: bool = True  # re-rank the search's finalists at the largest graph batch inside the captured step
     prefill_tokens: Optional[int] = None  # the scheduler's max_extend_tokens: library solution search at that chunk size too
+    weight_quant: Optional[str] = None  # "fp8_block128": qkv / o / gate_up / down as block-scaled e4m3 (model.DenseDecoder)
     seed: int = 42
 
     @property
@@ -266,7 +267,8 @@ class Engine:
         overlap = cfg.comm_overlap and not (cfg.tp_size > 1 and cfg.comm_split_tokens > 0 and cfg.comm_side is None)
         self.model = DenseDecoder(cfg.model, dtype=cfg.dtype, device=self.device, tp_rank=cfg.tp_rank,
                                   tp_size=cfg.tp_size, seed=cfg.seed, comm=comm, fused=cfg.fused_qkv_path,
-                                  comm_split_tokens=cfg.comm_split_tokens, comm_overlap=overlap)
+                                  comm_split_tokens=cfg.comm_split_tokens, comm_overlap=overlap,
+                                  weight_quant=cfg.weight_quant)
         if self.model.moe:  # the tall expert path's scratch counts as model memory, not as room for KV pages
             m = cfg.model
             ops.moe_reserve(self.device, cfg.prefill_tokens or 8192, m.num_experts, m.num_experts_per_tok, m.hidden_size,

@@ -96,6 +96,9 @@ PRESETS: Dict[str, ModelConfig] = {
 }
 
 
+_W8_PROJECTIONS = ("qkv", "o", "gate_up", "down")  # what weight_quant="fp8_block128" quantises
+
+
 @dataclass
 class LayerWeights:
     input_norm: torch.Tensor
@@ -165,8 +168,14 @@ class Communicator:
 class DenseDecoder:
     def __init__(self, cfg: ModelConfig, *, dtype: torch.dtype, device: torch.device, tp_rank: int = 0,
                  tp_size: int = 1, seed: int = 42, comm: Optional[Communicator] = None, fused: bool = True,
-                 init_std: float = 0.02, comm_split_tokens: int = 0, comm_overlap: bool = True) -> None:
+                 init_std: float = 0.02, comm_split_tokens: int = 0, comm_overlap: bool = True,
+                 weight_quant: Optional[str] = None) -> None:
         self.cfg, self.dtype, self.device = cfg, dtype, device
+        # "fp8_block128": qkv / o / gate_up / down are kept as ops.Fp8Weight (e4m3 bytes + one fp32 scale per 128 x 128
+        # block, the FP8 checkpoints' layout) and served by csrc/gemm_w8.hip; embedding, LM head and norms stay 16-bit
+        if weight_quant not in (None, "fp8_block128"):
+            raise ValueError(f"weight_quant {weight_quant!r}: None or 'fp8_block128'")
+        self.weight_quant = weight_quant
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self.fused = fused
         self.comm = comm or Communicator(None, tp_size)
@@ -198,6 +207,16 @@ class DenseDecoder:
         H = cfg.hidden_size
         self.moe = cfg.num_experts > 0
         self.moe_inter = heads_per_rank(cfg.moe_intermediate_size, tp_size) if self.moe else 0
+        if weight_quant:
+            if self.moe:
+                raise ValueError("weight_quant='fp8_block128' serves dense models only (the expert MLP kernels read 16-bit weights)")
+            if dtype != torch.bfloat16:
+                raise ValueError("weight_quant='fp8_block128' needs bf16 activations")
+            bad = {k: v for k, v in dict(q_dim=self.q_dim, kv_dim=self.kv_dim, intermediate=self.inter, hidden=H).items()
+                   if v % ops.W8_BLOCK}
+            if bad:
+                raise ValueError(f"weight_quant='fp8_block128' at tp {tp_size}: shard boundaries {bad} are not multiples of "
+                                 f"the {ops.W8_BLOCK} x {ops.W8_BLOCK} scale block")
         self.embed = w(self.vocab_tp, H)
         self.layers: List[LayerWeights] = []
         for _ in range(cfg.num_layers):
@@ -210,13 +229,21 @@ class DenseDecoder:
                                                 w1=w(E, 2 * self.moe_inter, H), w2=w(E, H, self.moe_inter)))
             else:
                 self.layers.append(LayerWeights(**attn, gate_up=w(2 * self.inter, H), down=w(H, self.inter)))
+            if weight_quant:  # layer by layer: the 16-bit originals of one layer at a time
+                for k in _W8_PROJECTIONS:
+                    setattr(self.layers[-1], k, ops.quantize_fp8_block128(getattr(self.layers[-1], k)))
         # gate_up rows in the block-32 interleaved order the fused projection + SiLU.mul epilogue needs (csrc/gemm_g3.hip);
         # every consumer goes through ops.linear_silu, the oracle gets the reference layout back (gate_up_reference)
-        self.gate_up_ilv = bool(fused and _FUSE_SILU and device.type == "cuda" and self.inter % 64 == 0 and not self.moe)
+        self.gate_up_ilv = bool(fused and _FUSE_SILU and device.type == "cuda" and self.inter % 64 == 0 and not self.moe
+                                and not weight_quant)
         if self.gate_up_ilv:
             idx = ops.gate_up_interleave_index(self.inter, device)
             for lw in self.layers:
                 lw.gate_up = lw.gate_up.index_select(0, idx)
+        if weight_quant and device.type == "cuda":
+            torch.cuda.empty_cache()  # the 16-bit originals: the freed memory is the KV pool's
+            # batches above 256 rows dequantise one weight at a time into this scratch
+            ops.w8_reserve(device, max(getattr(self.layers[0], k).q.numel() for k in _W8_PROJECTIONS))
         self.final_norm = ones(H)
         self.lm_head = self.embed if cfg.tie_word_embeddings else w(self.vocab_tp, H)
         self.cos_sin = fi.build_cos_sin_cache(D, cfg.max_position, cfg.rope_base, cfg.rope_scaling, device=device)
@@ -225,11 +252,14 @@ class DenseDecoder:
         n = self.embed.numel() + self.final_norm.numel()
         if not self.cfg.tie_word_embeddings:
             n += self.lm_head.numel()
+        w8 = 0  # quantised projections: one byte per weight plus the fp32 scales
         for lw in self.layers:
             mlp = (lw.router, lw.w1, lw.w2) if self.moe else (lw.gate_up, lw.down)
-            n += sum(t.numel() for t in (lw.input_norm, lw.qkv, lw.o, lw.post_norm) + mlp)
+            ts = (lw.input_norm, lw.qkv, lw.o, lw.post_norm) + mlp
+            n += sum(t.numel() for t in ts if not isinstance(t, ops.Fp8Weight))
+            w8 += sum(t.nbytes() for t in ts if isinstance(t, ops.Fp8Weight))
             n += 0 if lw.q_norm is None else lw.q_norm.numel() + lw.k_norm.numel()
-        return n * self.embed.element_size()
+        return n * self.embed.element_size() + w8
 
     def streamed_bytes_per_step(self, tokens: Optional[int] = None) -> int:
         """Weight bytes a decode step must read: everything but the embedding table (gathered rows only).  Expert
@@ -250,18 +280,37 @@ class DenseDecoder:
         (o, down) on dim 1, vocab shards of embed_tokens / lm_head, KV heads replicated when tp > Hkv."""
         cfg, r, n, D = self.cfg, self.tp_rank, self.tp_size, self.cfg.head_dim
 
-        def col(t):
+        def col(t, unit=1):  # unit = rows per entry of dim 0: 128 for a weight_scale_inv grid
             return t.chunk(n, dim=0)[r]
 
-        def kv(t):
+        def kv(t, unit=1):
             if cfg.num_kv_heads < n:
                 h = r * cfg.num_kv_heads // n
-                return t[h * D:(h + 1) * D]
+                return t[h * D // unit:(h + 1) * D // unit]
             return col(t)
+
+        def row(t, unit=1):
+            return t.chunk(n, dim=1)[r]
 
         def put(dst: torch.Tensor, src: torch.Tensor) -> None:
             assert dst.shape == src.shape, (dst.shape, src.shape)
+            if src.dtype == torch.float8_e4m3fn:
+                raise ValueError("the checkpoint holds FP8 weights: build the model with weight_quant='fp8_block128'")
             dst.copy_(src.to(device=self.device, dtype=self.dtype))
+
+        def put_w8(dst: "ops.Fp8Weight", parts) -> None:
+            """parts: (HF module name, shard function) merged along N.  FP8 entries bring their `weight_scale_inv` grid,
+            sharded by the same function (every shard boundary is a multiple of 128); 16-bit entries are quantised here."""
+            ws = [f(state[k + ".weight"]) for k, f in parts]
+            if ws[0].dtype == torch.float8_e4m3fn:
+                grid = torch.cat([f(state[k + ".weight_scale_inv"], ops.W8_BLOCK) for k, f in parts], dim=0)
+                new = ops.Fp8Weight(torch.cat([t.view(torch.uint8) for t in ws], dim=0).view(torch.float8_e4m3fn),
+                                    grid.to(torch.float32))
+            else:
+                new = ops.quantize_fp8_block128(torch.cat(ws, dim=0).to(device=self.device, dtype=self.dtype))
+            assert new.shape == dst.shape, (new.shape, dst.shape)
+            dst.q.view(torch.uint8).copy_(new.q.view(torch.uint8))  # in place: captured graphs hold these pointers
+            dst.scales.copy_(new.scales)
 
         start, length = self.vocab_range
         put(self.embed[:length], state["model.embed_tokens.weight"][start:start + length])
@@ -272,11 +321,17 @@ class DenseDecoder:
             p = f"model.layers.{i}."
             put(lw.input_norm, state[p + "input_layernorm.weight"])
             put(lw.post_norm, state[p + "post_attention_layernorm.weight"])
-            put(lw.qkv, torch.cat([col(state[p + "self_attn.q_proj.weight"]), kv(state[p + "self_attn.k_proj.weight"]),
-                                   kv(state[p + "self_attn.v_proj.weight"])], dim=0))
             if lw.q_norm is not None:
                 put(lw.q_norm, state[p + "self_attn.q_norm.weight"])
                 put(lw.k_norm, state[p + "self_attn.k_norm.weight"])
+            if self.weight_quant:
+                put_w8(lw.qkv, [(p + "self_attn.q_proj", col), (p + "self_attn.k_proj", kv), (p + "self_attn.v_proj", kv)])
+                put_w8(lw.o, [(p + "self_attn.o_proj", row)])
+                put_w8(lw.gate_up, [(p + "mlp.gate_proj", col), (p + "mlp.up_proj", col)])
+                put_w8(lw.down, [(p + "mlp.down_proj", row)])
+                continue
+            put(lw.qkv, torch.cat([col(state[p + "self_attn.q_proj.weight"]), kv(state[p + "self_attn.k_proj.weight"]),
+                                   kv(state[p + "self_attn.v_proj.weight"])], dim=0))
             put(lw.o, state[p + "self_attn.o_proj.weight"].chunk(n, dim=1)[r])
             if self.moe:  # P/models/weight.py:63-119: experts stacked on a new dim 0, each sharded like a dense gated MLP
                 ex = [p + f"mlp.experts.{e}." for e in range(cfg.num_experts)]
@@ -309,6 +364,8 @@ class DenseDecoder:
         fold = self.fused and self.tp_size == 1 and _ROWSTREAM_FUSE
         norm = {"fold": "norm"} if fold else {}
         act = {"fold": "act_interleaved" if self.gate_up_ilv else "act"} if fold else {}
+        if self.weight_quant:  # the W8A16 kernel's knobs are a fixed function of the shape: only the LM head is searched
+            return [("lm_head", [self.lm_head], self.cfg.hidden_size)]
         if self.moe:  # the expert MLP is ops.fused_moe: no gate_up / down projection to plan
             return [("qkv", [l.qkv for l in pick], self.cfg.hidden_size), ("o", [l.o for l in pick], self.q_dim),
                     ("lm_head", [self.lm_head], self.cfg.hidden_size)]
@@ -389,7 +446,9 @@ class DenseDecoder:
         # Measured inside the captured step (tools/small_batch_ab.py, profiles/r04_small_batch_ab.json): folding the norms is
         # worth 0.13 / 0.07-0.11 ms per step at one / two rows and nothing at four; SiLU.mul pays at one row only.
         T = x.shape[0]
-        rs_on = _ROWSTREAM_FUSE and self.fused and self.tp_size == 1 and T <= ops.ROWSTREAM_FOLD_NORM_MAX_M and not self.moe
+        # quantised projections take the plain chain: ops.linear, then the norm / activation / qk kernels as their own launches
+        rs_on = (_ROWSTREAM_FUSE and self.fused and self.tp_size == 1 and T <= ops.ROWSTREAM_FOLD_NORM_MAX_M and not self.moe
+                 and not self.weight_quant)
         pending: Optional[torch.Tensor] = None
         spare: Optional[torch.Tensor] = None
 

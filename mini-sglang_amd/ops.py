@@ -1085,10 +1085,130 @@ def silu_pair_us(x: torch.Tensor, weights, iters: int = 8) -> float:
     return _time_launches_us(lambda w: linear_silu(x, w, half), weights, iters, 3)
 
 
+# ---------------------------------------------------------------------------- block-scaled FP8 weights (csrc/gemm_w8.hip)
+W8_BLOCK = 128    # the checkpoints' scale block: weight_scale_inv is [N / 128, K / 128]
+W8_MAX_M = 256
+_W8_E4M3_MAX = 448.0
+_W8_CUS = 256     # the knob choice assumes the MI355X's CU count on every box, so that bits do not depend on the box
+_W8_SCRATCH: dict = {}
+
+
+class Fp8Weight:
+    """A projection weight as the FP8 checkpoints store it: `q` float8_e4m3fn [N, K] and `scales` fp32
+    [N / 128, K / 128] (`weight_scale_inv`); the weight is q * scales per 128 x 128 block."""
+    __slots__ = ("q", "scales", "shape")
+
+    def __init__(self, q: torch.Tensor, scales: torch.Tensor) -> None:
+        N, K = q.shape
+        if q.dtype != torch.float8_e4m3fn or scales.dtype != torch.float32:
+            raise TypeError(f"Fp8Weight wants float8_e4m3fn bytes and fp32 scales, got {q.dtype}, {scales.dtype}")
+        if N % W8_BLOCK or K % W8_BLOCK or tuple(scales.shape) != (N // W8_BLOCK, K // W8_BLOCK):
+            raise ValueError(f"Fp8Weight: weight {tuple(q.shape)} / scales {tuple(scales.shape)} are not whole 128 x 128 blocks")
+        self.q, self.scales, self.shape = q.contiguous(), scales.contiguous(), q.shape
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    def nbytes(self) -> int:
+        return self.q.numel() + 4 * self.scales.numel()
+
+    def dequantize(self) -> torch.Tensor:
+        """fp32 q * scales in plain torch (tests and the oracle; the device path is w8_dequant)."""
+        s = self.scales.cpu().repeat_interleave(W8_BLOCK, 0).repeat_interleave(W8_BLOCK, 1)
+        return (self.q.cpu().float() * s).to(self.device)
+
+
+def quantize_fp8_block128(w: torch.Tensor) -> Fp8Weight:
+    """Load-time quantiser: per 128 x 128 block s = max(amax, tiny) / 448 in fp32, q = (w / s) -> e4m3fn."""
+    N, K = w.shape
+    if N % W8_BLOCK or K % W8_BLOCK:
+        raise ValueError(f"quantize_fp8_block128: {N} x {K} is not a whole number of 128 x 128 blocks")
+    blocks = w.float().view(N // W8_BLOCK, W8_BLOCK, K // W8_BLOCK, W8_BLOCK)
+    s = blocks.abs().amax(dim=(1, 3)).clamp_min(torch.finfo(torch.float32).tiny) / _W8_E4M3_MAX
+    scaled = (blocks / s[:, None, :, None]).reshape(N, K)
+    try:
+        q = scaled.to(torch.float8_e4m3fn)
+    except RuntimeError:  # no device cast: load time, not the hot path
+        q = scaled.cpu().to(torch.float8_e4m3fn).to(w.device)
+    return Fp8Weight(q, s)
+
+
+def w8_plan(M: int, N: int, K: int) -> Tuple[int, int]:
+    """(k-slices, row tiles) of msgl_w8_gemm_nt: a fixed function of the shape (no timing search).  Row tiles share the
+    staged activations; k-slices are added until the launch has about four waves per CU, within the kernel's LDS limits."""
+    mt = 1 if M <= 16 else 2 if M <= 32 else 4 if M <= 64 else 8 if M <= 128 else 16
+    rows, per_wave = (M + 15) // 16 * 16, 2 if mt == 8 else 1
+    waves = N // (16 * per_wave)
+    slices = 1
+    while (waves * slices < 4 * _W8_CUS and slices < 8 and 2 * slices <= K // W8_BLOCK
+           and rows * 2 * slices * 256 <= 65536 and 2 * slices * per_wave * mt <= 64):
+        slices *= 2
+    tiles = 4
+    while tiles > 1 and (tiles * slices > 8 or tiles * slices * per_wave * mt > 64
+                         or (waves // tiles < _W8_CUS and (M <= 64 or tiles > 2))):  # M > 64: sharing x outweighs the grid
+        tiles //= 2
+    return slices, tiles
+
+
+def w8_gemm(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None, slices: Optional[int] = None,
+            row_tiles: Optional[int] = None) -> torch.Tensor:
+    """out[M, N] = x[M, K] @ (q * scales)[N, K]^T for 1 <= M <= 256, straight from the fp8 bytes."""
+    _need_cuda(x, w.q, w.scales)
+    M, K = x.shape
+    N = w.shape[0]
+    assert x.dim() == 2 and K == w.shape[1] and x.stride(1) == 1, (x.shape, w.shape)
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == x.dtype and out.is_cuda
+    plan = w8_plan(M, N, K)
+    check(
+        lib().msgl_w8_gemm_nt(out.data_ptr(), x.data_ptr(), w.q.data_ptr(), w.scales.data_ptr(), M, N, K, x.stride(0),
+                              w.q.stride(0), out.stride(0), _dt(x), slices or plan[0], row_tiles or plan[1], _stream()),
+        "w8_gemm_nt",
+    )
+    return out
+
+
+def w8_reserve(device: torch.device, numel: int) -> torch.Tensor:
+    """The bf16 scratch that batches above 256 rows dequantise a weight into; reserved at load time so that it counts
+    as model memory, grown here only if a larger weight shows up."""
+    key = torch.device(device).index or 0
+    buf = _W8_SCRATCH.get(key)
+    if buf is None or buf.numel() < numel:
+        buf = _W8_SCRATCH[key] = torch.empty(numel, dtype=torch.bfloat16, device=device)
+    return buf
+
+
+def w8_dequant(w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] = round(float(q) * scales), product in fp32 (msgl_w8_dequant)."""
+    _need_cuda(w.q, w.scales)
+    N, K = w.shape
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=w.device)
+    assert out.shape == (N, K) and out.stride(1) == 1 and out.dtype == torch.bfloat16 and out.is_cuda
+    check(lib().msgl_w8_dequant(out.data_ptr(), w.q.data_ptr(), w.scales.data_ptr(), N, K, w.q.stride(0), out.stride(0),
+                                _stream()), "w8_dequant")
+    return out
+
+
+def w8_linear(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if x.shape[0] == 0:
+        return x.new_empty((0, w.shape[0])) if out is None else out
+    if x.shape[0] <= W8_MAX_M:
+        _no_pending_slabs(x.device)
+        return w8_gemm(x, w, out)
+    N, K = w.shape
+    return linear(x, w8_dequant(w, w8_reserve(x.device, N * K)[: N * K].view(N, K)), out)
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[M, N] = x[M, K] @ w[N, K]^T (the reference's `F.linear`, P/layers/linear.py:32): the hand-written
     weight-streaming kernel where skinny_tune() planned it (decode batches <= 64), else msgl_gemm_nt with the
-    tuned library solution for the shape if gemm_tune() ran, else the library's heuristic."""
+    tuned library solution for the shape if gemm_tune() ran, else the library's heuristic.  An Fp8Weight goes to the
+    W8A16 kernel (M <= 256) or through its bf16 scratch copy (larger batches)."""
+    if isinstance(w, Fp8Weight):
+        return w8_linear(x, w, out)
     out, M, N, K = _gemm_args(x, w, out)
     if M == 0:
         return out
@@ -1123,6 +1243,8 @@ def linear_slabs(x: torch.Tensor, w: torch.Tensor):
     shape's plan is the k-sliced full-batch kernel (or, mid-size batches, the k-split weight-streaming kernel), the reduce
     launch is left to the norm (slabs is a Slabs, `out` is allocated but NOT yet written: pass both to
     fused_add_rmsnorm_slabs); otherwise (out, None) = linear(x, w)."""
+    if isinstance(w, Fp8Weight):  # the W8A16 kernel reduces its k-slices itself
+        return linear(x, w), None
     if _RO_PLAN:
         M, K, N = x.shape[0], x.shape[1], w.shape[0]
         plan = _RO_PLAN.get((x.device.index or 0, M, N, K, x.stride(0), w.stride(0), _dt(x)))
