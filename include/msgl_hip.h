@@ -46,7 +46,7 @@ extern "C" {
 /* dtype codes for logits */
 #define MSGL_F32 2
 
-#define MSGL_ABI_VERSION 6
+#define MSGL_ABI_VERSION 7
 
 /* Last error message of the calling thread ("" if none). */
 const char* msgl_last_error(void);
@@ -423,11 +423,26 @@ int msgl_ro_gemm_nt(void* out, const void* x, const void* w, int M, int N, int K
  *                    64 KB of LDS.  Deterministic, no atomics, no workspace, capturable; the grid depends on the
  *                    arguments only.
  *   msgl_w8_dequant:  out[n, k] = round_bf16(float(q[n, k]) * s[n/128, k/128]) (product in fp32), out [N, K] bf16 with
- *                    ldo % 8 == 0, 16-byte aligned: the 16-bit GEMM paths then serve batches above 256 rows.
+ *                    ldo % 8 == 0, 16-byte aligned: a 16-bit copy for the 16-bit GEMM paths.  Batches above 256 rows no
+ *                    longer need it: msgl_w8_tall_gemm_nt multiplies them straight from the fp8 bytes.
+ *   msgl_w8_tall_gemm_nt (csrc/gemm_w8_tall.hip): the same product, numerics, layouts, leading-dimension and alignment
+ *                    rules for ANY M >= 1.  A workgroup owns 128 weight rows (one scale row group, weights HBM -> VGPR)
+ *                    x `tm` (128 or 256) rows of x (double-buffered through LDS by DMA); grid = (N/128) x ceil(M/tm) x
+ *                    k_slices.  k_slices (1 .. min(K/128, 64)) cuts the K/128 blocks into contiguous balanced ranges;
+ *                    k_slices > 1 writes one fp32 slab [M][N] per slice into `workspace` (16-byte aligned, at least
+ *                    msgl_w8_tall_workspace_bytes) and a second kernel adds the slabs in slice order and rounds;
+ *                    k_slices == 1 writes `out` directly and takes no workspace.  The knobs change the fp32 summation
+ *                    order only.  Deterministic, no atomics, no allocation, no synchronisation, capturable; the grid
+ *                    depends on the arguments only.
+ *   msgl_w8_tall_workspace_bytes: k_slices * M * N * 4; 0 for k_slices == 1; < 0 outside the contract.
  * ---------------------------------------------------------------------- */
 int msgl_w8_gemm_nt(void* out, const void* x, const void* q, const float* scales, int M, int N, int K, int64_t ldx,
                     int64_t ldq, int64_t ldo, int dtype, int slices, int row_tiles, void* stream);
 int msgl_w8_dequant(void* out, const void* q, const float* scales, int N, int K, int64_t ldq, int64_t ldo, void* stream);
+int64_t msgl_w8_tall_workspace_bytes(int M, int N, int k_slices);
+int msgl_w8_tall_gemm_nt(void* out, const void* x, const void* q, const float* scales, int M, int N, int K, int64_t ldx,
+                         int64_t ldq, int64_t ldo, int dtype, int tm, int k_slices, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Mixture-of-experts MLP (csrc/moe.hip), bf16 with fp32 accumulation.  Replaces: FusedMoe.forward with activation "silu"

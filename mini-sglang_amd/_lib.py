@@ -24,7 +24,7 @@ BF16, FP16, F32 = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
 PREFILL_QTILE = 128
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _u64, _sz = C.c_uint64, C.c_size_t
@@ -108,6 +108,8 @@ HIP_SIGNATURES = {
     "msgl_ro_gemm_nt": (_i, [_p, _p, _p, _i, _i, _i, _l, _l, _l, _i, _i, _i, _i, _p, _l, _p]),
     "msgl_w8_gemm_nt": (_i, [_p, _p, _p, _p, _i, _i, _i, _l, _l, _l, _i, _i, _i, _p]),
     "msgl_w8_dequant": (_i, [_p, _p, _p, _i, _i, _l, _l, _p]),
+    "msgl_w8_tall_workspace_bytes": (_l, [_i, _i, _i]),
+    "msgl_w8_tall_gemm_nt": (_i, [_p, _p, _p, _p, _i, _i, _i, _l, _l, _l, _i, _i, _i, _p, _l, _p]),
     "msgl_moe_route": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "msgl_moe_workspace_bytes": (_l, [_i, _i, _i, _i, _i]),
     "msgl_moe_forward": (_i, [_p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),

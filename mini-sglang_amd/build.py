@@ -43,6 +43,7 @@ HIP_SOURCES = [
     "gemm_g3.hip",
     "gemm_ro.hip",
     "gemm_w8.hip",
+    "gemm_w8_tall.hip",
     "moe.hip",
     "moe_tall.hip",
     "comm_p2p.hip",

@@ -1171,8 +1171,8 @@ def w8_gemm(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None, s
 
 
 def w8_reserve(device: torch.device, numel: int) -> torch.Tensor:
-    """The bf16 scratch that batches above 256 rows dequantise a weight into; reserved at load time so that it counts
-    as model memory, grown here only if a larger weight shows up."""
+    """The bf16 scratch that batches above W8_TALL_MAX_M rows dequantise a weight into; reserved at load time so that it
+    counts as model memory, grown here only if a larger weight shows up."""
     key = torch.device(device).index or 0
     buf = _W8_SCRATCH.get(key)
     if buf is None or buf.numel() < numel:
@@ -1192,12 +1192,51 @@ def w8_dequant(w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor
     return out
 
 
+# The batches ops.linear hands to the tall-tile kernel (csrc/gemm_w8_tall.hip): measured (tools/w8_bench.py,
+# profiles/w8_bench.json) as the range in which it beats the other route by PLAN_MARGIN on all four Qwen3-14B
+# projections.  Below: msgl_w8_gemm_nt (gate_up is faster there up to 16 rows); above: msgl_w8_dequant + the 16-bit linear.
+W8_TALL_MIN_M = 32
+W8_TALL_MAX_M = 256
+
+
+def w8_tall_plan(M: int, N: int, K: int) -> Tuple[int, int]:
+    """(tm, k_slices) of msgl_w8_tall_gemm_nt: a fixed function of the shape (no timing search, 256 CUs assumed on every
+    box).  tm = 256 rows of x per workgroup above 128 rows, else 128.  k-slices fill the machine when the tile grid is
+    small: as many as keep the launch within one workgroup per CU at tm = 256 (128 KB of LDS each) or two at tm = 128
+    (64 KB), at least two 128-k blocks per slice, at most 16.  tiles * k_slices <= 512 bounds the slabs by 64 MB."""
+    tm = 256 if M > 128 else 128
+    tiles = (N // W8_BLOCK) * ((M + tm - 1) // tm)
+    target = _W8_CUS * (1 if tm == 256 else 2)
+    return tm, max(1, min(K // (2 * W8_BLOCK), 16, target // tiles))
+
+
+def w8_tall_gemm(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None, tm: Optional[int] = None,
+                 k_slices: Optional[int] = None) -> torch.Tensor:
+    """out[M, N] = x[M, K] @ (q * scales)[N, K]^T for any M >= 1, straight from the fp8 bytes (msgl_w8_tall_gemm_nt)."""
+    _need_cuda(x, w.q, w.scales)
+    M, K = x.shape
+    N = w.shape[0]
+    assert x.dim() == 2 and K == w.shape[1] and x.stride(1) == 1, (x.shape, w.shape)
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == x.dtype and out.is_cuda
+    plan = w8_tall_plan(M, N, K)
+    ws = gemm_workspace(x.device)
+    check(
+        lib().msgl_w8_tall_gemm_nt(out.data_ptr(), x.data_ptr(), w.q.data_ptr(), w.scales.data_ptr(), M, N, K, x.stride(0),
+                                   w.q.stride(0), out.stride(0), _dt(x), tm or plan[0], k_slices or plan[1], ws.data_ptr(),
+                                   ws.numel(), _stream()),
+        "w8_tall_gemm_nt",
+    )
+    return out
+
+
 def w8_linear(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     if x.shape[0] == 0:
         return x.new_empty((0, w.shape[0])) if out is None else out
-    if x.shape[0] <= W8_MAX_M:
+    if x.shape[0] <= W8_TALL_MAX_M:
         _no_pending_slabs(x.device)
-        return w8_gemm(x, w, out)
+        return w8_gemm(x, w, out) if x.shape[0] < W8_TALL_MIN_M else w8_tall_gemm(x, w, out)
     N, K = w.shape
     return linear(x, w8_dequant(w, w8_reserve(x.device, N * K)[: N * K].view(N, K)), out)
 
@@ -1206,7 +1245,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None)
     """out[M, N] = x[M, K] @ w[N, K]^T (the reference's `F.linear`, P/layers/linear.py:32): the hand-written
     weight-streaming kernel where skinny_tune() planned it (decode batches <= 64), else msgl_gemm_nt with the
     tuned library solution for the shape if gemm_tune() ran, else the library's heuristic.  An Fp8Weight goes to the
-    W8A16 kernel (M <= 256) or through its bf16 scratch copy (larger batches)."""
+    W8A16 kernel (M < W8_TALL_MIN_M), the tall-tile W8A16 kernel (up to W8_TALL_MAX_M) or through its bf16 scratch copy."""
     if isinstance(w, Fp8Weight):
         return w8_linear(x, w, out)
     out, M, N, K = _gemm_args(x, w, out)

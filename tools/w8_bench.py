@@ -1,12 +1,14 @@
-"""msgl_w8_gemm_nt (block-scaled e4m3 weights, csrc/gemm_w8.hip) against today's ops.linear on bf16 weights, at the four
-Qwen3-14B projection shapes and M in {1, 8, 64, 256}.
+"""The W8A16 kernels (block-scaled e4m3 weights) against today's ops.linear on bf16 weights, at the four Qwen3-14B
+projection shapes and M in {1, 8, 16, 32, 64, 128, 256, 512, 2048}.  Columns: `bf16`; `w8` = the route before the tall-tile
+kernel existed (msgl_w8_gemm_nt up to 256 rows, msgl_w8_dequant + the 16-bit ops.linear above); `tall` =
+msgl_w8_tall_gemm_nt (csrc/gemm_w8_tall.hip) with ops.w8_tall_plan.
 
     python tools/w8_bench.py [--out profiles/w8_bench.json] [--layers 6] [--replays 24] [--rounds 9]
 
 Same process, same box, alternating: per (shape, M) the bf16 side first runs the project's plan search for the shape
 (model.tune_gemms' search: library solutions and the hand-written 16-bit kernels), then both sides are captured as
 `--replays` calls per graph rotating over `--layers` weight sets (so weights come from HBM, not the Infinity Cache), and
-the two graphs are replayed in turn `--rounds` times; medians of the per-call time.  Algorithmic bytes = the weight (and
+the three graphs are replayed in turn `--rounds` times; medians of the per-call time.  Algorithmic bytes = the weight (and
 scale) bytes plus x in and out.  No GPU: fails, nothing is estimated."""
 from __future__ import annotations
 
@@ -52,7 +54,7 @@ def capture(fn, weights, replays: int):
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / "w8_bench.json"))
-    ap.add_argument("--batches", default="1,8,64,256")
+    ap.add_argument("--batches", default="1,8,16,32,64,128,256,512,2048")
     ap.add_argument("--layers", type=int, default=6)
     ap.add_argument("--replays", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=9)
@@ -72,8 +74,12 @@ def main() -> None:
             x = torch.randn((M, K), generator=g, device=dev).bfloat16()
             out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
             rep = gemm_plan.tune_projection_gemms([(name, bf16, K)], [M], "heuristic", torch.bfloat16, dev)[0]
+            scratch = ops.w8_reserve(dev, N * K)[: N * K].view(N, K)
+            old = (lambda w: ops.w8_gemm(x, w, out=out)) if M <= ops.W8_MAX_M else (
+                lambda w: ops.linear(x, ops.w8_dequant(w, scratch), out=out))
             graphs = {"bf16": capture(lambda w: ops.linear(x, w, out=out), bf16, args.replays),
-                      "w8": capture(lambda w: ops.w8_gemm(x, w, out=out), fp8, args.replays)}
+                      "w8": capture(old, fp8, args.replays),
+                      "tall": capture(lambda w: ops.w8_tall_gemm(x, w, out=out), fp8, args.replays)}
             samples = {k: [] for k in graphs}
             for _ in range(args.rounds):
                 for k, gr in graphs.items():
@@ -81,23 +87,27 @@ def main() -> None:
             us = {k: statistics.median(v) for k, v in samples.items()}
             last = (args.replays - 1) % args.layers
             ref = x.float() @ fp8[last].dequantize().t()
-            rel = ((out.float() - ref).abs().max() / ref.abs().max()).item()  # `out` holds the w8 graph's last call
+            rel = ((out.float() - ref).abs().max() / ref.abs().max()).item()  # `out` holds the tall graph's last call
             nbytes = {"bf16": 2 * N * K, "w8": fp8[0].nbytes()}
             io = 2 * M * (N + K)
             rows.append(dict(name=name, M=M, N=N, K=K, bf16_us=round(us["bf16"], 2), w8_us=round(us["w8"], 2),
-                             w8_speedup=round(us["bf16"] / us["w8"], 3), bf16_kernel=rep["kernel"][:120],
-                             w8_plan=list(ops.w8_plan(M, N, K)),
+                             tall_us=round(us["tall"], 2), w8_speedup=round(us["bf16"] / us["w8"], 3),
+                             tall_speedup=round(us["bf16"] / us["tall"], 3), tall_over_w8=round(us["tall"] / us["w8"], 3),
+                             bf16_kernel=rep["kernel"][:120],
+                             w8_plan=list(ops.w8_plan(M, N, K)) if M <= ops.W8_MAX_M else "dequant + linear",
+                             tall_plan=list(ops.w8_tall_plan(M, N, K)),
                              bf16_bytes_per_s=round((nbytes["bf16"] + io) / (us["bf16"] * 1e-6)),
                              w8_bytes_per_s=round((nbytes["w8"] + io) / (us["w8"] * 1e-6)),
                              w8_fraction_of_8TBps=round((nbytes["w8"] + io) / (us["w8"] * 1e-6) / PEAK_BYTES_PER_S, 4),
                              w8_spread_us=[round(min(samples["w8"]), 2), round(max(samples["w8"]), 2)],
+                             tall_spread_us=[round(min(samples["tall"]), 2), round(max(samples["tall"]), 2)],
                              bf16_spread_us=[round(min(samples["bf16"]), 2), round(max(samples["bf16"]), 2)],
-                             w8_max_rel_err_vs_fp32=round(rel, 5)))
+                             tall_max_rel_err_vs_fp32=round(rel, 5)))
             print(json.dumps(rows[-1]), flush=True)
             del graphs
         del bf16, fp8
     result = dict(model=cfg.name, device=torch.cuda.get_device_name(0), command="python tools/w8_bench.py",
-                  method=f"{args.replays} calls per captured graph over {args.layers} weight sets, the bf16 and the w8 graph "
+                  method=f"{args.replays} calls per captured graph over {args.layers} weight sets, the bf16, w8 and tall graphs "
                          f"replayed in turn, median of {args.rounds} replays each; bf16 = ops.linear after the project's plan "
                          f"search for the shape", rows=rows)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
