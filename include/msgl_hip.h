@@ -46,7 +46,7 @@ extern "C" {
 /* dtype codes for logits */
 #define MSGL_F32 2
 
-#define MSGL_ABI_VERSION 7
+#define MSGL_ABI_VERSION 8
 
 /* Last error message of the calling thread ("" if none). */
 const char* msgl_last_error(void);
@@ -483,6 +483,22 @@ int64_t msgl_moe_workspace_bytes_tall(int T, int E, int k, int hidden, int I_l);
 int msgl_moe_forward_tall(const void* x, const void* w1, const void* w2, const float* topk_weights, const int32_t* topk_ids,
                           void* workspace, int64_t workspace_bytes, void* out, int T, int E, int k, int hidden, int I_l,
                           void* stream);
+
+/* ------------------------------------------------------------------------
+ * The expert MLP with block-scaled FP8 expert weights (csrc/moe_w8.hip, W8A16): msgl_moe_forward with
+ *   w1[e] = q1[e] * s1[e] and w2[e] = q2[e] * s2[e] per 128 x 128 block, the FP8 checkpoints' layout.
+ *   q1 e4m3 bytes [E, 2 I_l, hidden] ([gate; up] row order), s1 fp32 [E, 2 I_l / 128, hidden / 128];
+ *   q2 e4m3 bytes [E, hidden, I_l], s2 fp32 [E, hidden / 128, I_l / 128]; x, out contiguous bf16.
+ *   msgl_moe_w8_forward: the contract and conventions of msgl_moe_forward with hidden % 128 == 0 and I_l % 128 == 0
+ *                    (MSGL_EINVAL before any launch otherwise, and for null or misaligned pointers: x, q1, q2, out 16 bytes,
+ *                    the scale grids 4).  e4m3 -> bf16 is exact; the MFMAs of a 128-k block start from zero and their sum
+ *                    enters the fp32 accumulator through one fma(scale, part, acc): a scaled weight is never rounded.
+ *   msgl_moe_w8_workspace_bytes: as msgl_moe_workspace_bytes (the same layout), under the stricter shape contract.
+ * ---------------------------------------------------------------------- */
+int64_t msgl_moe_w8_workspace_bytes(int T, int E, int k, int hidden, int I_l);
+int msgl_moe_w8_forward(const void* x, const void* q1, const float* s1, const void* q2, const float* s2,
+                        const float* topk_weights, const int32_t* topk_ids, void* workspace, int64_t workspace_bytes,
+                        void* out, int T, int E, int k, int hidden, int I_l, void* stream);
 
 /* ------------------------------------------------------------------------
  * Native radix prefix tree (libmsgl_hip.so, csrc/radix.cpp; host code, no device work).

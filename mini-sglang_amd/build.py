@@ -46,6 +46,7 @@ HIP_SOURCES = [
     "gemm_w8_tall.hip",
     "moe.hip",
     "moe_tall.hip",
+    "moe_w8.hip",
     "comm_p2p.hip",
 ]
 COMM_SOURCES = ["comm.cpp"]

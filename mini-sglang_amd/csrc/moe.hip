@@ -26,22 +26,15 @@
 //
 // A pair's result depends on its own row only: k in order, one accumulator per (pair, column), slots added in order.  Hence
 // bit-repeatable and independent of the rest of the batch.  No float atomics anywhere.
-#include "common.h"
+#include "moe_tables.h"
 
 namespace msgl {
 
 typedef __attribute__((ext_vector_type(4))) float moe_f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 moe_bf16x8;
 
-constexpr int kMoeMaxExperts = 256;
-constexpr int kMoeMaxTopk = 8;
-constexpr int kMoeBM = 16;             // row-block height: every expert's run of pairs is padded to it
-constexpr int kMoeItemBlocks = 4;      // row blocks per work item
-constexpr int kMoeItemRows = kMoeBM * kMoeItemBlocks;
 constexpr int kMoeChunkK = 256;        // k extent of one LDS stage
 constexpr int kMoeRowBytes = kMoeChunkK * 2 + 16;  // +16: consecutive rows start four banks apart
-constexpr int kMoeAlignWaves = 16;
-constexpr int kMoeMaxGridY = 65535;
 
 // ---------------------------------------------------------------------------------------------------------------- route
 template <bool kF32>
@@ -115,15 +108,6 @@ __global__ __launch_bounds__(256) void moe_route_kernel(float* __restrict__ weig
 }
 
 // ---------------------------------------------------------------------------------------------------------------- align
-struct MoeTables {
-  int32_t* sorted;       // [cap]  pair index, or -1 (pad), grouped by expert, stable in pair index
-  int32_t* lpos;         // [P]    scratch: a pair's rank among its wave segment's pairs of the same expert
-  int32_t* item_expert;  // [max_items]
-  int32_t* item_pos;     // [max_items]  first position in `sorted` (and row of `act`)
-  int32_t* item_blocks;  // [max_items]  1 .. 4 row blocks
-  int32_t* n_items;      // [1]
-};
-
 __global__ __launch_bounds__(64 * kMoeAlignWaves) void moe_align_kernel(const MoeTables tb, const int32_t* __restrict__ ids,
                                                                         int P, int E) {
   __shared__ int cnt[kMoeAlignWaves][kMoeMaxExperts];  // per (wave segment, expert): count, then exclusive prefix over waves
@@ -343,40 +327,13 @@ __global__ __launch_bounds__(256) void moe_sum_kernel(uint16_t* __restrict__ out
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static inline int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
-
-struct MoeLayout {
-  int64_t cap, max_items;
-  int64_t o_sorted, o_lpos, o_iexp, o_ipos, o_iblk, o_nitems, o_act, o_partial, bytes;
-};
-
-// a pure function of the arguments: positions after padding every expert's run to 16 <= P + 15 min(E, P); an item holds at
-// least one pair and every item but an expert's last holds 64, so items <= min(E, P) + P / 64
-static MoeLayout moe_layout(int64_t T, int64_t E, int64_t k, int64_t hidden, int64_t I) {
-  MoeLayout L;
-  const int64_t P = T * k, ne = E < P ? E : P;
-  L.cap = P + (kMoeBM - 1) * ne;
-  L.max_items = ne + P / kMoeItemRows;
-  int64_t o = 0;
-  L.o_sorted = o; o += up256(L.cap * 4);
-  L.o_lpos = o; o += up256(P * 4);
-  L.o_iexp = o; o += up256(L.max_items * 4);
-  L.o_ipos = o; o += up256(L.max_items * 4);
-  L.o_iblk = o; o += up256(L.max_items * 4);
-  L.o_nitems = o; o += 256;
-  L.o_act = o; o += up256(L.cap * I * 2);
-  L.o_partial = o; o += up256(P * hidden * 4);
-  L.bytes = o;
-  return L;
+void moe_launch_align(const MoeTables& tb, const int32_t* ids, int P, int E, hipStream_t s) {
+  moe_align_kernel<<<dim3(1), dim3(64 * kMoeAlignWaves), 0, s>>>(tb, ids, P, E);
 }
 
-static int moe_check_shape(const char* who, int64_t T, int64_t E, int64_t k, int64_t hidden, int64_t I) {
-  MSGL_REQUIRE(T >= 1 && T * k < (1ll << 30), "%s: T = %lld outside [1, 2^30 / k)", who, (long long)T);
-  MSGL_REQUIRE(E >= 1 && E <= kMoeMaxExperts, "%s: E = %lld outside [1, %d]", who, (long long)E, kMoeMaxExperts);
-  MSGL_REQUIRE(k >= 1 && k <= kMoeMaxTopk && k <= E, "%s: k = %lld outside [1, min(%d, E)]", who, (long long)k, kMoeMaxTopk);
-  MSGL_REQUIRE(hidden >= 64 && hidden % 64 == 0, "%s: hidden = %lld must be a multiple of 64", who, (long long)hidden);
-  MSGL_REQUIRE(I >= 32 && I % 32 == 0, "%s: the expert intermediate size %lld must be a multiple of 32", who, (long long)I);
-  return MSGL_OK;
+void moe_launch_sum(uint16_t* out, const float* partial, const int32_t* ids, int T, int k, int E, int hidden, hipStream_t s) {
+  const int64_t threads = (int64_t)T * (hidden / 8);
+  moe_sum_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(out, partial, ids, T, k, E, hidden);
 }
 
 }  // namespace msgl
@@ -420,16 +377,10 @@ extern "C" int msgl_moe_forward(const void* x, const void* w1, const void* w2, c
                "moe_forward: needs %lld workspace bytes, 256-byte aligned", (long long)L.bytes);
   MSGL_REQUIRE(aligned16(x) && aligned16(w1) && aligned16(w2) && aligned16(out), "moe_forward: pointers must be 16-byte aligned");
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  MoeTables tb;
-  tb.sorted = reinterpret_cast<int32_t*>(ws + L.o_sorted);
-  tb.lpos = reinterpret_cast<int32_t*>(ws + L.o_lpos);
-  tb.item_expert = reinterpret_cast<int32_t*>(ws + L.o_iexp);
-  tb.item_pos = reinterpret_cast<int32_t*>(ws + L.o_ipos);
-  tb.item_blocks = reinterpret_cast<int32_t*>(ws + L.o_iblk);
-  tb.n_items = reinterpret_cast<int32_t*>(ws + L.o_nitems);
+  const MoeTables tb = moe_tables(ws, L);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int P = T * k;
-  moe_align_kernel<<<dim3(1), dim3(64 * kMoeAlignWaves), 0, s>>>(tb, topk_ids, P, E);
+  moe_launch_align(tb, topk_ids, P, E, s);
   MSGL_CHECK_LAUNCH("moe_forward(align)");
 
   MoeGemmParams g;
@@ -448,9 +399,7 @@ extern "C" int msgl_moe_forward(const void* x, const void* w1, const void* w2, c
   else
     moe_gemm_kernel<MOE_DOWN, 1><<<g2, dim3(256), 0, s>>>(g);
   MSGL_CHECK_LAUNCH("moe_forward(down)");
-  const int64_t threads = (int64_t)T * (hidden / 8);
-  moe_sum_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(static_cast<uint16_t*>(out), g.partial, topk_ids,
-                                                                               T, k, E, hidden);
+  moe_launch_sum(static_cast<uint16_t*>(out), g.partial, topk_ids, T, k, E, hidden, s);
   MSGL_CHECK_LAUNCH("moe_forward(sum)");
   return MSGL_OK;
 }

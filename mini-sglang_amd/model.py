@@ -96,7 +96,8 @@ PRESETS: Dict[str, ModelConfig] = {
 }
 
 
-_W8_PROJECTIONS = ("qkv", "o", "gate_up", "down")  # what weight_quant="fp8_block128" quantises
+_W8_PROJECTIONS = ("qkv", "o", "gate_up", "down")  # what weight_quant="fp8_block128" quantises in a dense model
+_W8_MOE_PROJECTIONS = ("qkv", "o", "w1", "w2")     # ... and in an expert model (the router stays 16-bit)
 
 
 @dataclass
@@ -172,7 +173,8 @@ class DenseDecoder:
                  weight_quant: Optional[str] = None) -> None:
         self.cfg, self.dtype, self.device = cfg, dtype, device
         # "fp8_block128": qkv / o / gate_up / down are kept as ops.Fp8Weight (e4m3 bytes + one fp32 scale per 128 x 128
-        # block, the FP8 checkpoints' layout) and served by csrc/gemm_w8.hip; embedding, LM head and norms stay 16-bit
+        # block, the FP8 checkpoints' layout) and served by csrc/gemm_w8.hip; embedding, LM head and norms stay 16-bit.
+        # An expert model keeps w1 / w2 as expert-stacked Fp8Weights (csrc/moe_w8.hip) and its router 16-bit
         if weight_quant not in (None, "fp8_block128"):
             raise ValueError(f"weight_quant {weight_quant!r}: None or 'fp8_block128'")
         self.weight_quant = weight_quant
@@ -207,12 +209,16 @@ class DenseDecoder:
         H = cfg.hidden_size
         self.moe = cfg.num_experts > 0
         self.moe_inter = heads_per_rank(cfg.moe_intermediate_size, tp_size) if self.moe else 0
+        self.w8_names = () if not weight_quant else _W8_MOE_PROJECTIONS if self.moe else _W8_PROJECTIONS
         if weight_quant:
-            if self.moe:
-                raise ValueError("weight_quant='fp8_block128' serves dense models only (the expert MLP kernels read 16-bit weights)")
             if dtype != torch.bfloat16:
                 raise ValueError("weight_quant='fp8_block128' needs bf16 activations")
-            bad = {k: v for k, v in dict(q_dim=self.q_dim, kv_dim=self.kv_dim, intermediate=self.inter, hidden=H).items()
+            if self.moe and (self.moe_inter % ops.W8_BLOCK or H % ops.W8_BLOCK):
+                raise ValueError(f"weight_quant='fp8_block128' at tp {tp_size}: expert shards of {self.moe_inter} rows (hidden {H}) "
+                                 f"are not whole {ops.W8_BLOCK} x {ops.W8_BLOCK} blocks; FP8 covers the dense projections and the "
+                                 "experts together or not at all")
+            mlp = {} if self.moe else dict(intermediate=self.inter)  # an expert model has no dense MLP
+            bad = {k: v for k, v in dict(q_dim=self.q_dim, kv_dim=self.kv_dim, hidden=H, **mlp).items()
                    if v % ops.W8_BLOCK}
             if bad:
                 raise ValueError(f"weight_quant='fp8_block128' at tp {tp_size}: shard boundaries {bad} are not multiples of "
@@ -230,7 +236,7 @@ class DenseDecoder:
             else:
                 self.layers.append(LayerWeights(**attn, gate_up=w(2 * self.inter, H), down=w(H, self.inter)))
             if weight_quant:  # layer by layer: the 16-bit originals of one layer at a time
-                for k in _W8_PROJECTIONS:
+                for k in self.w8_names:
                     setattr(self.layers[-1], k, ops.quantize_fp8_block128(getattr(self.layers[-1], k)))
         # gate_up rows in the block-32 interleaved order the fused projection + SiLU.mul epilogue needs (csrc/gemm_g3.hip);
         # every consumer goes through ops.linear_silu, the oracle gets the reference layout back (gate_up_reference)
@@ -243,7 +249,9 @@ class DenseDecoder:
         if weight_quant and device.type == "cuda":
             torch.cuda.empty_cache()  # the 16-bit originals: the freed memory is the KV pool's
             # batches above 256 rows dequantise one weight at a time into this scratch
-            ops.w8_reserve(device, max(getattr(self.layers[0], k).q.numel() for k in _W8_PROJECTIONS))
+            ops.w8_reserve(device, max(getattr(self.layers[0], k).q.numel() for k in ("qkv", "o") + (() if self.moe else ("gate_up", "down"))))
+            if self.moe:  # the tall route dequantises one layer's expert stacks
+                ops.moe_w8_reserve(device, cfg.num_experts, H, self.moe_inter)
         self.final_norm = ones(H)
         self.lm_head = self.embed if cfg.tie_word_embeddings else w(self.vocab_tp, H)
         self.cos_sin = fi.build_cos_sin_cache(D, cfg.max_position, cfg.rope_base, cfg.rope_scaling, device=device)
@@ -270,7 +278,10 @@ class DenseDecoder:
             b -= self.embed.numel() * self.embed.element_size()
         if self.moe and tokens is not None:
             idle = self.cfg.num_experts - min(self.cfg.num_experts, tokens * self.cfg.num_experts_per_tok)
-            b -= sum(idle * (lw.w1[0].numel() + lw.w2[0].numel()) for lw in self.layers) * self.embed.element_size()
+            if self.weight_quant:  # 1 B per weight + 4 B per block, the same for every expert
+                b -= sum(idle * (lw.w1.nbytes() + lw.w2.nbytes()) // self.cfg.num_experts for lw in self.layers)
+            else:
+                b -= sum(idle * (lw.w1[0].numel() + lw.w2[0].numel()) for lw in self.layers) * self.embed.element_size()
         return b
 
     # ------------------------------------------------------------------ weights from a checkpoint
@@ -327,6 +338,13 @@ class DenseDecoder:
             if self.weight_quant:
                 put_w8(lw.qkv, [(p + "self_attn.q_proj", col), (p + "self_attn.k_proj", kv), (p + "self_attn.v_proj", kv)])
                 put_w8(lw.o, [(p + "self_attn.o_proj", row)])
+                if self.moe:  # every expert like a dense gated MLP, written into its slice of the stacks
+                    put(lw.router, state[p + "mlp.gate.weight"])
+                    for e in range(cfg.num_experts):
+                        q = p + f"mlp.experts.{e}."
+                        put_w8(ops.Fp8Weight(lw.w1.q[e], lw.w1.scales[e]), [(q + "gate_proj", col), (q + "up_proj", col)])
+                        put_w8(ops.Fp8Weight(lw.w2.q[e], lw.w2.scales[e]), [(q + "down_proj", row)])
+                    continue
                 put_w8(lw.gate_up, [(p + "mlp.gate_proj", col), (p + "mlp.up_proj", col)])
                 put_w8(lw.down, [(p + "mlp.down_proj", row)])
                 continue

@@ -1095,14 +1095,17 @@ _W8_SCRATCH: dict = {}
 
 class Fp8Weight:
     """A projection weight as the FP8 checkpoints store it: `q` float8_e4m3fn [N, K] and `scales` fp32
-    [N / 128, K / 128] (`weight_scale_inv`); the weight is q * scales per 128 x 128 block."""
+    [N / 128, K / 128] (`weight_scale_inv`); the weight is q * scales per 128 x 128 block.  An expert stack has a leading
+    dimension: q [E, N, K], scales [E, N / 128, K / 128] (viewed as [E N, K] it is a valid 2-D weight, N % 128 == 0)."""
     __slots__ = ("q", "scales", "shape")
 
     def __init__(self, q: torch.Tensor, scales: torch.Tensor) -> None:
-        N, K = q.shape
+        if q.dim() not in (2, 3):
+            raise ValueError(f"Fp8Weight: weight {tuple(q.shape)} must be [N, K] or [E, N, K]")
+        N, K = q.shape[-2:]
         if q.dtype != torch.float8_e4m3fn or scales.dtype != torch.float32:
             raise TypeError(f"Fp8Weight wants float8_e4m3fn bytes and fp32 scales, got {q.dtype}, {scales.dtype}")
-        if N % W8_BLOCK or K % W8_BLOCK or tuple(scales.shape) != (N // W8_BLOCK, K // W8_BLOCK):
+        if N % W8_BLOCK or K % W8_BLOCK or tuple(scales.shape) != tuple(q.shape[:-2]) + (N // W8_BLOCK, K // W8_BLOCK):
             raise ValueError(f"Fp8Weight: weight {tuple(q.shape)} / scales {tuple(scales.shape)} are not whole 128 x 128 blocks")
         self.q, self.scales, self.shape = q.contiguous(), scales.contiguous(), q.shape
 
@@ -1115,12 +1118,16 @@ class Fp8Weight:
 
     def dequantize(self) -> torch.Tensor:
         """fp32 q * scales in plain torch (tests and the oracle; the device path is w8_dequant)."""
-        s = self.scales.cpu().repeat_interleave(W8_BLOCK, 0).repeat_interleave(W8_BLOCK, 1)
+        s = self.scales.cpu().repeat_interleave(W8_BLOCK, -2).repeat_interleave(W8_BLOCK, -1)
         return (self.q.cpu().float() * s).to(self.device)
 
 
 def quantize_fp8_block128(w: torch.Tensor) -> Fp8Weight:
     """Load-time quantiser: per 128 x 128 block s = max(amax, tiny) / 448 in fp32, q = (w / s) -> e4m3fn."""
+    if w.dim() == 3:  # an expert stack: every expert on its own (N % 128 == 0, so no block spans two experts)
+        E, N, K = w.shape
+        flat = quantize_fp8_block128(w.reshape(E * N, K))
+        return Fp8Weight(flat.q.view(E, N, K), flat.scales.view(E, N // W8_BLOCK, K // W8_BLOCK))
     N, K = w.shape
     if N % W8_BLOCK or K % W8_BLOCK:
         raise ValueError(f"quantize_fp8_block128: {N} x {K} is not a whole number of 128 x 128 blocks")
@@ -1573,6 +1580,12 @@ def moe_workspace_bytes(T: int, E: int, k: int, hidden: int, inter: int) -> int:
     return int(n)
 
 
+def moe_w8_workspace_bytes(T: int, E: int, k: int, hidden: int, inter: int) -> int:
+    n = lib().msgl_moe_w8_workspace_bytes(T, E, k, hidden, inter)
+    check(int(n), "moe_w8_workspace_bytes")
+    return int(n)
+
+
 # The tall path (csrc/moe_tall.hip) keeps its scratch in a buffer of its own, one per device, grown on demand up to
 # MOE_WORKSPACE_MAX_BYTES: Qwen3-30B-A3B at 8192 tokens needs 103 MB of act, which leaves room for two column slabs.
 _MOE_WS: dict = {}
@@ -1581,6 +1594,11 @@ MOE_WORKSPACE_MAX_BYTES = 512 << 20
 # the routing).  Measured with tools/moe_bench.py on Qwen3-30B-A3B: T = 1024 (64 pairs per expert) is the smallest batch where
 # the tall path wins by more than the 2 % box-to-box noise; at 512 the rows path is still ahead.
 MOE_TALL_MIN_PAIRS_PER_EXPERT = 64
+# FP8 experts (csrc/moe_w8.hip): from here on impl None dequantises the stacks and takes the bf16 tall path.  Measured with
+# tools/moe_bench.py --w8 on Qwen3-30B-A3B (profiles/moe_w8_bench.json): the dequantisation of a layer's stacks costs about
+# 0.3 ms, so at T = 1024 (64 pairs per expert) the FP8 rows kernel is still twice as fast; T = 8192 (512 pairs per expert) is
+# the smallest measured batch where dequant + tall wins by more than the 2 % box-to-box noise.
+MOE_W8_TALL_MIN_PAIRS_PER_EXPERT = 512
 
 
 def moe_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
@@ -1630,7 +1648,23 @@ def _moe_tall_chunk(T: int, E: int, k: int, hidden: int, inter: int, nbytes: int
     return lo
 
 
-def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits: torch.Tensor, topk: int,
+def moe_w8_reserve(device: torch.device, E: int, hidden: int, inter: int) -> torch.Tensor:
+    """The bf16 scratch the tall route of FP8 experts dequantises one layer's w1 and w2 into (3 E hidden inter elements);
+    reserved at load time so that it counts as model memory and is never allocated during capture."""
+    return w8_reserve(device, 3 * E * hidden * inter)
+
+
+def _moe_w8_dequant(w1: "Fp8Weight", w2: "Fp8Weight") -> Tuple[torch.Tensor, torch.Tensor]:
+    E, hidden, inter = w2.shape
+    n1 = E * 2 * inter * hidden
+    buf = moe_w8_reserve(w1.device, E, hidden, inter)
+    d1, d2 = buf[:n1].view(E * 2 * inter, hidden), buf[n1:n1 + E * hidden * inter].view(E * hidden, inter)
+    w8_dequant(Fp8Weight(w1.q.view(E * 2 * inter, hidden), w1.scales.view(-1, hidden // W8_BLOCK)), d1)
+    w8_dequant(Fp8Weight(w2.q.view(E * hidden, inter), w2.scales.view(-1, inter // W8_BLOCK)), d2)
+    return d1.view(E, 2 * inter, hidden), d2.view(E, hidden, inter)
+
+
+def fused_moe(x: torch.Tensor, w1, w2, router_logits: torch.Tensor, topk: int,
               renormalize: bool, out: Optional[torch.Tensor] = None, impl: Optional[str] = None) -> torch.Tensor:
     """The expert MLP of FusedMoe.forward (P/moe/fused.py:230-256; SiLU experts, router weight on the output):
     x [T, hidden], w1 [E, 2 I, hidden] ([gate; up] rows), w2 [E, hidden, I], router_logits [T, E] -> [T, hidden].
@@ -1642,12 +1676,29 @@ def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits
     impl "tall": csrc/moe_tall.hip, 256-row items for prefill, the same bits.  Scratch comes from moe_workspace(); the
     down projection runs per column slab of `hidden`, as wide as the buffer allows, and only a batch that does not fit
     at 128 columns runs as token chunks.
-    impl None: "tall" where T k >= MOE_TALL_MIN_PAIRS_PER_EXPERT E, else "rows".  `out` may be `x`."""
+    impl None: "tall" where T k >= MOE_TALL_MIN_PAIRS_PER_EXPERT E, else "rows".  `out` may be `x`.
+    w1 and w2 are both bf16 tensors or both expert-stacked Fp8Weights (hidden and I multiples of 128).  FP8 "rows" is
+    csrc/moe_w8.hip, straight from the e4m3 bytes; FP8 "tall" dequantises both stacks into the reserved scratch
+    (moe_w8_reserve) and runs the bf16 tall kernel on it, bit-equal to fused_moe on dequantize().bfloat16(); impl None
+    switches at MOE_W8_TALL_MIN_PAIRS_PER_EXPERT."""
     assert impl in (None, "rows", "tall"), f"fused_moe: impl must be None, 'rows' or 'tall', not {impl!r}"
-    _need_cuda(x, w1, w2, router_logits)
-    assert x.dim() == 2 and w1.dim() == 3 and w2.dim() == 3 and router_logits.dim() == 2
-    assert x.dtype == w1.dtype == w2.dtype == torch.bfloat16, "fused_moe: bf16 activations and expert weights only"
-    assert x.is_contiguous() and w1.is_contiguous() and w2.is_contiguous() and router_logits.is_contiguous()
+    w8 = isinstance(w1, Fp8Weight)
+    assert w8 == isinstance(w2, Fp8Weight), "fused_moe: w1 and w2 must both be bf16 tensors or both Fp8Weight"
+    if w8:
+        _need_cuda(x, w1.q, w1.scales, w2.q, w2.scales, router_logits)
+        assert x.dtype == torch.bfloat16, "fused_moe: bf16 activations only"
+        assert len(w1.shape) == 3 and len(w2.shape) == 3, "fused_moe: FP8 experts are [E, N, K] stacks"
+        if impl is None:
+            impl = "tall" if x.shape[0] * topk >= MOE_W8_TALL_MIN_PAIRS_PER_EXPERT * w2.shape[0] else "rows"
+        if impl == "tall" and x.shape[0]:
+            w1, w2 = _moe_w8_dequant(w1, w2)
+            w8 = False
+    else:
+        _need_cuda(x, w1, w2, router_logits)
+        assert x.dtype == w1.dtype == w2.dtype == torch.bfloat16, "fused_moe: bf16 activations and expert weights only"
+        assert w1.is_contiguous() and w2.is_contiguous()
+    assert x.dim() == 2 and len(w1.shape) == 3 and len(w2.shape) == 3 and router_logits.dim() == 2
+    assert x.is_contiguous() and router_logits.is_contiguous()
     T, hidden = x.shape
     E, inter = w2.shape[0], w2.shape[2]
     assert w1.shape == (E, 2 * inter, hidden) and w2.shape == (E, hidden, inter) and router_logits.shape == (T, E)
@@ -1683,7 +1734,7 @@ def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits
     chunk = min(T, MOE_MAX_CHUNK_TOKENS)
     while True:  # routing results (256-byte aligned) sit in front of the kernels' own scratch
         route_bytes = 2 * ((chunk * topk * 4 + 255) // 256 * 256)
-        need = moe_workspace_bytes(chunk, E, topk, hidden, inter)
+        need = (moe_w8_workspace_bytes if w8 else moe_workspace_bytes)(chunk, E, topk, hidden, inter)
         if route_bytes + need <= ws.numel() or chunk == 1:
             break
         chunk = (chunk + 1) // 2
@@ -1694,6 +1745,15 @@ def fused_moe(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, router_logits
         weights = ws[:n * topk * 4].view(torch.float32).view(n, topk)
         ids = ws[route_bytes // 2:route_bytes // 2 + n * topk * 4].view(torch.int32).view(n, topk)
         _moe_route_into(weights, ids, router_logits[t0:t0 + n], topk, renormalize)
+        if w8:
+            check(
+                lib().msgl_moe_w8_forward(x[t0:t0 + n].data_ptr(), w1.q.data_ptr(), w1.scales.data_ptr(), w2.q.data_ptr(),
+                                          w2.scales.data_ptr(), weights.data_ptr(), ids.data_ptr(), base + route_bytes,
+                                          ws.numel() - route_bytes, out[t0:t0 + n].data_ptr(), n, E, topk, hidden, inter,
+                                          _stream()),
+                "moe_w8_forward",
+            )
+            continue
         check(
             lib().msgl_moe_forward(x[t0:t0 + n].data_ptr(), w1.data_ptr(), w2.data_ptr(), weights.data_ptr(), ids.data_ptr(),
                                    base + route_bytes, ws.numel() - route_bytes, out[t0:t0 + n].data_ptr(), n, E, topk, hidden,

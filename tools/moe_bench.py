@@ -9,7 +9,13 @@ experts would otherwise be served from the Infinity Cache), device events around
 Baseline, same process and box: index_select -> F.linear -> silu * mul -> F.linear -> index_add_ per expert.  The routing
 and the per-expert row lists are made before the timed region (they need the host to know the group sizes), so a timed pass
 is eager launches only, no host sync; median of `--rounds` passes.
-Algorithmic bytes = the touched experts' w1 and w2 plus x in and out.  No GPU: fails, nothing is estimated."""
+Algorithmic bytes = the touched experts' w1 and w2 plus x in and out.  No GPU: fails, nothing is estimated.
+
+    python tools/moe_bench.py --w8 [--out profiles/moe_w8_bench.json] [--tokens 1,16,64,256,1024,8192]
+
+`--w8`: the same layer with block-scaled FP8 experts (csrc/moe_w8.hip).  Per T one captured graph each for bf16 fused_moe
+(impl=None), FP8 impl="rows" and, from T = 256, FP8 impl="tall" (dequantise + csrc/moe_tall.hip); the graphs are replayed in
+turn, round by round, in this one process, median per graph.  FP8 bytes = 1 per expert weight + 4 per block."""
 from __future__ import annotations
 
 import argparse
@@ -62,6 +68,56 @@ def torch_loop(x, w1, w2, groups, out):
     return out.copy_(acc)
 
 
+def w8_main(args, dev) -> None:
+    cfg = PRESETS["qwen3-30b-a3b"]
+    H, I, E, k = cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts, cfg.num_experts_per_tok
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def rnd(*shape, std):
+        return (torch.randn(shape, generator=g, device=dev) * std).bfloat16()
+
+    sets = [(rnd(E, 2 * I, H, std=H ** -0.5), rnd(E, H, I, std=I ** -0.5)) for _ in range(args.layers)]
+    qsets = [(ops.quantize_fp8_block128(w1), ops.quantize_fp8_block128(w2)) for w1, w2 in sets]
+    ops.moe_w8_reserve(dev, E, H, I)
+    rows = []
+    for T in [int(t) for t in args.tokens.split(",")]:
+        x, logits, out = rnd(T, H, std=1.0), rnd(T, E, std=1.0), torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        replays = args.replays if T <= 256 else 4
+        cases = [("bf16", sets, None), ("w8_rows", qsets, "rows")] + ([("w8_tall", qsets, "tall")] if T >= 256 else [])
+        graphs, outs = {}, {}
+        for name, ws, impl in cases:
+            for w1, w2 in ws:
+                ops.fused_moe(x, w1, w2, logits, k, cfg.norm_topk_prob, out=out, impl=impl)
+            torch.cuda.synchronize()
+            graphs[name] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[name]):
+                for i in range(replays):
+                    ops.fused_moe(x, *ws[i % len(ws)], logits, k, cfg.norm_topk_prob, out=out, impl=impl)
+            graphs[name].replay()
+            outs[name] = out.clone()
+        samples = {name: [] for name in graphs}
+        for _ in range(args.rounds):  # in turn: every round sees the box in the same state for all three
+            for name, graph in graphs.items():
+                samples[name].append(timed_us(graph.replay, 1, replays))
+        us = {name: statistics.median(v) for name, v in samples.items()}
+        _, ids = ops.moe_route(logits, k, cfg.norm_topk_prob)
+        touched = int(ids.unique().numel())
+        w8_bytes = touched * (3 * I * H + 4 * 3 * I * H // (128 * 128)) + 2 * T * H * 2
+        ref = outs["bf16"].float()
+        rows.append(dict(T=T, experts_touched=touched, **{f"{n}_us": round(v, 2) for n, v in us.items()},
+                         w8_rows_over_bf16=round(us["w8_rows"] / us["bf16"], 3), w8_algorithmic_bytes=w8_bytes,
+                         w8_rows_fraction_of_8TBps=round(w8_bytes / (us["w8_rows"] * 1e-6) / PEAK_BYTES_PER_S, 4),
+                         bf16_fraction_of_8TBps=round((touched * 3 * I * H * 2 + 2 * T * H * 2) / (us["bf16"] * 1e-6) / PEAK_BYTES_PER_S, 4),
+                         max_rel_diff_vs_bf16=round((outs["w8_rows"].float() - ref).abs().max().item() / ref.abs().max().item(), 5)))
+        print(json.dumps(rows[-1]), flush=True)
+        del graphs
+    result = dict(model=cfg.name, hidden=H, moe_intermediate=I, experts=E, topk=k, device=torch.cuda.get_device_name(0),
+                  method=f"{args.replays} calls per captured graph (4 at T > 256) over {args.layers} weight sets; the bf16, FP8 rows "
+                         f"and FP8 tall graphs replayed in turn, median of {args.rounds} rounds", rows=rows)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / "moe_bench.json"))
@@ -70,9 +126,12 @@ def main() -> None:
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--w8", action="store_true", help="FP8 experts against bf16 (see the module docstring)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "moe_bench needs the GPU"
     dev = torch.device("cuda:0")
+    if args.w8:
+        return w8_main(args, dev)
     cfg = PRESETS["qwen3-30b-a3b"]
     H, I, E, k = cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts, cfg.num_experts_per_tok
     g = torch.Generator(device=dev).manual_seed(0)
