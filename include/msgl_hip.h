@@ -46,7 +46,7 @@ extern "C" {
 /* dtype codes for logits */
 #define MSGL_F32 2
 
-#define MSGL_ABI_VERSION 8
+#define MSGL_ABI_VERSION 9
 
 /* Last error message of the calling thread ("" if none). */
 const char* msgl_last_error(void);
@@ -494,11 +494,19 @@ int msgl_moe_forward_tall(const void* x, const void* w1, const void* w2, const f
  *                    the scale grids 4).  e4m3 -> bf16 is exact; the MFMAs of a 128-k block start from zero and their sum
  *                    enters the fp32 accumulator through one fma(scale, part, acc): a scaled weight is never rounded.
  *   msgl_moe_w8_workspace_bytes: as msgl_moe_workspace_bytes (the same layout), under the stricter shape contract.
+ *   msgl_moe_w8_forward_tall (csrc/moe_w8_tall.hip): the same product for prefill-sized batches, BIT-IDENTICAL to
+ *                    msgl_moe_w8_forward: 256-row work items, weights HBM -> registers, activations global -> LDS by DMA.
+ *                    Arguments, layouts, alignment rules and refusals of msgl_moe_w8_forward; workspace contract and slab
+ *                    rule of msgl_moe_forward_tall (minimum msgl_moe_workspace_bytes_tall, the same layout).  Capturable,
+ *                    no atomics, nothing allocated.
  * ---------------------------------------------------------------------- */
 int64_t msgl_moe_w8_workspace_bytes(int T, int E, int k, int hidden, int I_l);
 int msgl_moe_w8_forward(const void* x, const void* q1, const float* s1, const void* q2, const float* s2,
                         const float* topk_weights, const int32_t* topk_ids, void* workspace, int64_t workspace_bytes,
                         void* out, int T, int E, int k, int hidden, int I_l, void* stream);
+int msgl_moe_w8_forward_tall(const void* x, const void* q1, const float* s1, const void* q2, const float* s2,
+                             const float* topk_weights, const int32_t* topk_ids, void* workspace, int64_t workspace_bytes,
+                             void* out, int T, int E, int k, int hidden, int I_l, void* stream);
 
 /* ------------------------------------------------------------------------
  * Native radix prefix tree (libmsgl_hip.so, csrc/radix.cpp; host code, no device work).

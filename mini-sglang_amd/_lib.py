@@ -24,7 +24,7 @@ BF16, FP16, F32 = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
 PREFILL_QTILE = 128
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _u64, _sz = C.c_uint64, C.c_size_t
@@ -117,6 +117,7 @@ HIP_SIGNATURES = {
     "msgl_moe_forward_tall": (_i, [_p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
     "msgl_moe_w8_workspace_bytes": (_l, [_i, _i, _i, _i, _i]),
     "msgl_moe_w8_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
+    "msgl_moe_w8_forward_tall": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
 }
 
 COMM_SIGNATURES = {

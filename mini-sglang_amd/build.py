@@ -47,6 +47,7 @@ HIP_SOURCES = [
     "moe.hip",
     "moe_tall.hip",
     "moe_w8.hip",
+    "moe_w8_tall.hip",
     "comm_p2p.hip",
 ]
 COMM_SOURCES = ["comm.cpp"]

@@ -1594,11 +1594,12 @@ MOE_WORKSPACE_MAX_BYTES = 512 << 20
 # the routing).  Measured with tools/moe_bench.py on Qwen3-30B-A3B: T = 1024 (64 pairs per expert) is the smallest batch where
 # the tall path wins by more than the 2 % box-to-box noise; at 512 the rows path is still ahead.
 MOE_TALL_MIN_PAIRS_PER_EXPERT = 64
-# FP8 experts (csrc/moe_w8.hip): from here on impl None dequantises the stacks and takes the bf16 tall path.  Measured with
-# tools/moe_bench.py --w8 on Qwen3-30B-A3B (profiles/moe_w8_bench.json): the dequantisation of a layer's stacks costs about
-# 0.3 ms, so at T = 1024 (64 pairs per expert) the FP8 rows kernel is still twice as fast; T = 8192 (512 pairs per expert) is
-# the smallest measured batch where dequant + tall wins by more than the 2 % box-to-box noise.
-MOE_W8_TALL_MIN_PAIRS_PER_EXPERT = 512
+# FP8 experts: from here on impl None takes the native FP8 tall kernel (csrc/moe_w8_tall.hip, "tall_w8") instead of the FP8
+# rows kernel (csrc/moe_w8.hip); the two give the same bits.  Measured with tools/moe_bench.py --w8 on Qwen3-30B-A3B
+# (profiles/moe_w8_tall_bench.json): at T = 1024 (64 pairs per expert) rows is still ahead (401 vs 407 us); T = 2048 (128
+# pairs per expert) is the smallest measured batch where the tall kernel wins by more than the 2 % box-to-box noise (591 vs
+# 792 us).
+MOE_W8_TALL_MIN_PAIRS_PER_EXPERT = 128
 
 
 def moe_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
@@ -1678,10 +1679,12 @@ def fused_moe(x: torch.Tensor, w1, w2, router_logits: torch.Tensor, topk: int,
     at 128 columns runs as token chunks.
     impl None: "tall" where T k >= MOE_TALL_MIN_PAIRS_PER_EXPERT E, else "rows".  `out` may be `x`.
     w1 and w2 are both bf16 tensors or both expert-stacked Fp8Weights (hidden and I multiples of 128).  FP8 "rows" is
-    csrc/moe_w8.hip, straight from the e4m3 bytes; FP8 "tall" dequantises both stacks into the reserved scratch
-    (moe_w8_reserve) and runs the bf16 tall kernel on it, bit-equal to fused_moe on dequantize().bfloat16(); impl None
-    switches at MOE_W8_TALL_MIN_PAIRS_PER_EXPERT."""
-    assert impl in (None, "rows", "tall"), f"fused_moe: impl must be None, 'rows' or 'tall', not {impl!r}"
+    csrc/moe_w8.hip, straight from the e4m3 bytes; FP8 "tall_w8" (Fp8Weight only) is csrc/moe_w8_tall.hip, 256-row items
+    straight from the e4m3 bytes with the scratch and slabs of "tall", the same bits as FP8 "rows"; FP8 "tall" dequantises
+    both stacks into the reserved scratch (moe_w8_reserve) and runs the bf16 tall kernel on it, bit-equal to fused_moe on
+    dequantize().bfloat16() (not to the other two: the scaled weight is rounded to bf16).  FP8 impl None: "tall_w8" where
+    T k >= MOE_W8_TALL_MIN_PAIRS_PER_EXPERT E, else "rows"."""
+    assert impl in (None, "rows", "tall", "tall_w8"), f"fused_moe: impl must be None, 'rows', 'tall' or 'tall_w8', not {impl!r}"
     w8 = isinstance(w1, Fp8Weight)
     assert w8 == isinstance(w2, Fp8Weight), "fused_moe: w1 and w2 must both be bf16 tensors or both Fp8Weight"
     if w8:
@@ -1689,11 +1692,12 @@ def fused_moe(x: torch.Tensor, w1, w2, router_logits: torch.Tensor, topk: int,
         assert x.dtype == torch.bfloat16, "fused_moe: bf16 activations only"
         assert len(w1.shape) == 3 and len(w2.shape) == 3, "fused_moe: FP8 experts are [E, N, K] stacks"
         if impl is None:
-            impl = "tall" if x.shape[0] * topk >= MOE_W8_TALL_MIN_PAIRS_PER_EXPERT * w2.shape[0] else "rows"
+            impl = "tall_w8" if x.shape[0] * topk >= MOE_W8_TALL_MIN_PAIRS_PER_EXPERT * w2.shape[0] else "rows"
         if impl == "tall" and x.shape[0]:
             w1, w2 = _moe_w8_dequant(w1, w2)
             w8 = False
     else:
+        assert impl != "tall_w8", "fused_moe: impl 'tall_w8' needs Fp8Weight expert stacks"
         _need_cuda(x, w1, w2, router_logits)
         assert x.dtype == w1.dtype == w2.dtype == torch.bfloat16, "fused_moe: bf16 activations and expert weights only"
         assert w1.is_contiguous() and w2.is_contiguous()
@@ -1710,7 +1714,7 @@ def fused_moe(x: torch.Tensor, w1, w2, router_logits: torch.Tensor, topk: int,
     _no_pending_slabs(x.device)
     if impl is None:
         impl = "tall" if T * topk >= MOE_TALL_MIN_PAIRS_PER_EXPERT * E else "rows"
-    if impl == "tall":
+    if impl in ("tall", "tall_w8"):
         ws = moe_reserve(x.device, min(T, MOE_MAX_CHUNK_TOKENS), E, topk, hidden, inter)
         limit = min(ws.numel(), MOE_WORKSPACE_MAX_BYTES)
         chunk = _moe_tall_chunk(min(T, MOE_MAX_CHUNK_TOKENS), E, topk, hidden, inter, limit)
@@ -1723,6 +1727,15 @@ def fused_moe(x: torch.Tensor, w1, w2, router_logits: torch.Tensor, topk: int,
             weights = ws[:n * topk * 4].view(torch.float32).view(n, topk)
             ids = ws[route_bytes // 2:route_bytes // 2 + n * topk * 4].view(torch.int32).view(n, topk)
             _moe_route_into(weights, ids, router_logits[t0:t0 + n], topk, renormalize)
+            if w8:
+                check(
+                    lib().msgl_moe_w8_forward_tall(x[t0:t0 + n].data_ptr(), w1.q.data_ptr(), w1.scales.data_ptr(),
+                                                   w2.q.data_ptr(), w2.scales.data_ptr(), weights.data_ptr(), ids.data_ptr(),
+                                                   base + route_bytes, limit - route_bytes, out[t0:t0 + n].data_ptr(), n, E,
+                                                   topk, hidden, inter, _stream()),
+                    "moe_w8_forward_tall",
+                )
+                continue
             check(
                 lib().msgl_moe_forward_tall(x[t0:t0 + n].data_ptr(), w1.data_ptr(), w2.data_ptr(), weights.data_ptr(),
                                             ids.data_ptr(), base + route_bytes, limit - route_bytes,

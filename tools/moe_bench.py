@@ -11,11 +11,12 @@ and the per-expert row lists are made before the timed region (they need the hos
 is eager launches only, no host sync; median of `--rounds` passes.
 Algorithmic bytes = the touched experts' w1 and w2 plus x in and out.  No GPU: fails, nothing is estimated.
 
-    python tools/moe_bench.py --w8 [--out profiles/moe_w8_bench.json] [--tokens 1,16,64,256,1024,8192]
+    python tools/moe_bench.py --w8 [--out profiles/moe_w8_tall_bench.json] [--tokens 256,512,1024,2048,4096,8192]
 
 `--w8`: the same layer with block-scaled FP8 experts (csrc/moe_w8.hip).  Per T one captured graph each for bf16 fused_moe
-(impl=None), FP8 impl="rows" and, from T = 256, FP8 impl="tall" (dequantise + csrc/moe_tall.hip); the graphs are replayed in
-turn, round by round, in this one process, median per graph.  FP8 bytes = 1 per expert weight + 4 per block."""
+(impl=None), FP8 impl="rows" and, from T = 256, FP8 impl="tall" (dequantise + csrc/moe_tall.hip) and FP8 impl="tall_w8"
+(csrc/moe_w8_tall.hip, `w8_tall_native`, checked to be the bits of FP8 rows); the graphs are replayed in turn, round by
+round, in this one process, median per graph.  FP8 bytes = 1 per expert weight + 4 per block."""
 from __future__ import annotations
 
 import argparse
@@ -83,7 +84,9 @@ def w8_main(args, dev) -> None:
     for T in [int(t) for t in args.tokens.split(",")]:
         x, logits, out = rnd(T, H, std=1.0), rnd(T, E, std=1.0), torch.empty((T, H), dtype=torch.bfloat16, device=dev)
         replays = args.replays if T <= 256 else 4
-        cases = [("bf16", sets, None), ("w8_rows", qsets, "rows")] + ([("w8_tall", qsets, "tall")] if T >= 256 else [])
+        cases = [("bf16", sets, None), ("w8_rows", qsets, "rows")]
+        if T >= 256:
+            cases += [("w8_tall", qsets, "tall"), ("w8_tall_native", qsets, "tall_w8")]
         graphs, outs = {}, {}
         for name, ws, impl in cases:
             for w1, w2 in ws:
@@ -104,16 +107,19 @@ def w8_main(args, dev) -> None:
         touched = int(ids.unique().numel())
         w8_bytes = touched * (3 * I * H + 4 * 3 * I * H // (128 * 128)) + 2 * T * H * 2
         ref = outs["bf16"].float()
+        native = dict(tall_native_equals_rows=bool(torch.equal(outs["w8_tall_native"], outs["w8_rows"])),
+                      w8_tall_native_over_rows=round(us["w8_tall_native"] / us["w8_rows"], 3),
+                      w8_tall_native_over_bf16=round(us["w8_tall_native"] / us["bf16"], 3)) if "w8_tall_native" in us else {}
         rows.append(dict(T=T, experts_touched=touched, **{f"{n}_us": round(v, 2) for n, v in us.items()},
-                         w8_rows_over_bf16=round(us["w8_rows"] / us["bf16"], 3), w8_algorithmic_bytes=w8_bytes,
+                         w8_rows_over_bf16=round(us["w8_rows"] / us["bf16"], 3), **native, w8_algorithmic_bytes=w8_bytes,
                          w8_rows_fraction_of_8TBps=round(w8_bytes / (us["w8_rows"] * 1e-6) / PEAK_BYTES_PER_S, 4),
                          bf16_fraction_of_8TBps=round((touched * 3 * I * H * 2 + 2 * T * H * 2) / (us["bf16"] * 1e-6) / PEAK_BYTES_PER_S, 4),
                          max_rel_diff_vs_bf16=round((outs["w8_rows"].float() - ref).abs().max().item() / ref.abs().max().item(), 5)))
         print(json.dumps(rows[-1]), flush=True)
         del graphs
     result = dict(model=cfg.name, hidden=H, moe_intermediate=I, experts=E, topk=k, device=torch.cuda.get_device_name(0),
-                  method=f"{args.replays} calls per captured graph (4 at T > 256) over {args.layers} weight sets; the bf16, FP8 rows "
-                         f"and FP8 tall graphs replayed in turn, median of {args.rounds} rounds", rows=rows)
+                  method=f"{args.replays} calls per captured graph (4 at T > 256) over {args.layers} weight sets; the bf16, FP8 rows, "
+                         f"FP8 dequant + tall and FP8 native tall graphs replayed in turn, median of {args.rounds} rounds", rows=rows)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
