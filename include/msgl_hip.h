@@ -46,7 +46,7 @@ extern "C" {
 /* dtype codes for logits */
 #define MSGL_F32 2
 
-#define MSGL_ABI_VERSION 9
+#define MSGL_ABI_VERSION 10
 
 /* Last error message of the calling thread ("" if none). */
 const char* msgl_last_error(void);
@@ -443,6 +443,34 @@ int64_t msgl_w8_tall_workspace_bytes(int M, int N, int k_slices);
 int msgl_w8_tall_gemm_nt(void* out, const void* x, const void* q, const float* scales, int M, int N, int K, int64_t ldx,
                          int64_t ldq, int64_t ldo, int dtype, int tm, int k_slices, void* workspace,
                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * W8A8 projection (csrc/gemm_w8a8.hip): the FP8 checkpoints' own inference numerics (activation_scheme "dynamic",
+ * weight_block_size [128, 128]) on the FP8 matrix instruction v_mfma_f32_16x16x128_f8f6f4.
+ *   msgl_a8_quant:   x [M, K] bf16 (dtype must be MSGL_BF16, row stride ldx elements, ldx % 8 == 0, 16-byte aligned) ->
+ *                    xq [M, K] OCP e4m3 bytes (row stride ldxq bytes, ldxq % 16 == 0, 16-byte aligned) and
+ *                    sx [M, K/128] contiguous fp32, one scale per token and 128-column group:
+ *                      sx[m, b] = max(amax_{k in block b} |x[m, k]|, FLT_MIN) / 448     (correctly rounded fp32 division)
+ *                      xq[m, k] = e4m3(float(x[m, k]) / sx[m, k/128])                   (fp32 division, round to nearest even;
+ *                                 a quotient an ulp above 448 lands on 448, the NaN encoding is never produced)
+ *                    K % 128 == 0, M >= 1, M * K/128 < 2^28.  One launch, no workspace, no atomics, capturable; the grid
+ *                    depends on the arguments only.  Bytes of xq outside [M, K] are not touched.
+ *   msgl_w8a8_gemm_nt: out[m, n] = round_bf16( sum_b sx[m, b] * s[n/128, b] * sum_{k in block b} float(xq[m, k]) * float(q[n, k]) )
+ *                    for ANY M >= 1, N % 128 == 0, K % 128 == 0.  xq, sx in the layout above; q [N, K] e4m3 bytes and scales
+ *                    [N/128, K/128] contiguous fp32 as for msgl_w8_gemm_nt; out [M, N] bf16 (dtype must be MSGL_BF16).
+ *                    ldxq % 16 == 0, ldq % 16 == 0, ldo % 4 == 0; xq / q 16-byte, out 8-byte, sx / scales 4-byte aligned.
+ *                    The inner sum of a block is one FP8 MFMA that starts from zero; it enters the fp32 sum through one
+ *                    FMA with sx * s.  A workgroup owns 128 weight rows x `tm` (128 or 256) rows of xq; grid = (N/128) x
+ *                    ceil(M/tm) x k_slices; k_slices, `workspace` and the reduce launch exactly as for
+ *                    msgl_w8_tall_gemm_nt.  The knobs change the fp32 summation order only.  Deterministic, no atomics, no
+ *                    allocation, no synchronisation, capturable; the grid depends on the arguments only.
+ *   msgl_w8a8_workspace_bytes: k_slices * M * N * 4; 0 for k_slices == 1; < 0 outside the contract.
+ * ---------------------------------------------------------------------- */
+int msgl_a8_quant(void* xq, float* sx, const void* x, int M, int K, int64_t ldx, int64_t ldxq, int dtype, void* stream);
+int64_t msgl_w8a8_workspace_bytes(int M, int N, int k_slices);
+int msgl_w8a8_gemm_nt(void* out, const void* xq, const float* sx, const void* q, const float* scales, int M, int N, int K,
+                      int64_t ldxq, int64_t ldq, int64_t ldo, int dtype, int tm, int k_slices, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Mixture-of-experts MLP (csrc/moe.hip), bf16 with fp32 accumulation.  Replaces: FusedMoe.forward with activation "silu"

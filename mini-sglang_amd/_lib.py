@@ -24,7 +24,7 @@ BF16, FP16, F32 = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
 PREFILL_QTILE = 128
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _u64, _sz = C.c_uint64, C.c_size_t
@@ -110,6 +110,9 @@ HIP_SIGNATURES = {
     "msgl_w8_dequant": (_i, [_p, _p, _p, _i, _i, _l, _l, _p]),
     "msgl_w8_tall_workspace_bytes": (_l, [_i, _i, _i]),
     "msgl_w8_tall_gemm_nt": (_i, [_p, _p, _p, _p, _i, _i, _i, _l, _l, _l, _i, _i, _i, _p, _l, _p]),
+    "msgl_a8_quant": (_i, [_p, _p, _p, _i, _i, _l, _l, _i, _p]),
+    "msgl_w8a8_workspace_bytes": (_l, [_i, _i, _i]),
+    "msgl_w8a8_gemm_nt": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _l, _l, _l, _i, _i, _i, _p, _l, _p]),
     "msgl_moe_route": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "msgl_moe_workspace_bytes": (_l, [_i, _i, _i, _i, _i]),
     "msgl_moe_forward": (_i, [_p, _p, _p, _p, _p, _p, _l, _p, _i, _i, _i, _i, _i, _p]),

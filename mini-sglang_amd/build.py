@@ -44,6 +44,7 @@ HIP_SOURCES = [
     "gemm_ro.hip",
     "gemm_w8.hip",
     "gemm_w8_tall.hip",
+    "gemm_w8a8.hip",
     "moe.hip",
     "moe_tall.hip",
     "moe_w8.hip",

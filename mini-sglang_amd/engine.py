@@ -123,7 +123,9 @@ class EngineConfig:
     gemm_tune: str = "heuristic"  # "off" | "heuristic" | "full": library solution search per graph batch size
     refine_in_graph: bool = True  # re-rank the search's finalists at the largest graph batch inside the captured step
     prefill_tokens: Optional[int] = None  # the scheduler's max_extend_tokens: library solution search at that chunk size too
-    weight_quant: Optional[str] = None  # "fp8_block128": qkv / o and gate_up / down or the experts as block-scaled e4m3 (model.DenseDecoder)
+    # "fp8_block128": qkv / o and gate_up / down or the experts as block-scaled e4m3; "fp8_block128_a8": dense models, the
+    # projections' activations as e4m3 per (token, 128 columns) as well (model.DenseDecoder)
+    weight_quant: Optional[str] = None
     seed: int = 42
 
     @property
@@ -275,6 +277,8 @@ class Engine:
                             self.model.moe_inter)
             if cfg.weight_quant:  # FP8 experts: the tall route's bf16 copy of one layer's stacks, model memory as well
                 ops.moe_w8_reserve(self.device, m.num_experts, m.hidden_size, self.model.moe_inter)
+        if cfg.weight_quant == "fp8_block128_a8":  # the quantised activations of a prefill chunk: model memory as well
+            ops.a8_reserve(self.device, cfg.prefill_tokens or 8192, max(cfg.model.hidden_size, self.model.q_dim, self.model.inter))
         torch.cuda.synchronize(self.device)
         free_after = self._agreed_free_memory(torch.cuda.mem_get_info(self.device)[0])
 

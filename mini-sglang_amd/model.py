@@ -175,8 +175,13 @@ class DenseDecoder:
         # "fp8_block128": qkv / o / gate_up / down are kept as ops.Fp8Weight (e4m3 bytes + one fp32 scale per 128 x 128
         # block, the FP8 checkpoints' layout) and served by csrc/gemm_w8.hip; embedding, LM head and norms stay 16-bit.
         # An expert model keeps w1 / w2 as expert-stacked Fp8Weights (csrc/moe_w8.hip) and its router 16-bit
-        if weight_quant not in (None, "fp8_block128"):
-            raise ValueError(f"weight_quant {weight_quant!r}: None or 'fp8_block128'")
+        # "fp8_block128_a8": the same weights, and the dense projections also quantise their activations per (token,
+        # 128-column group) at the batches ops.W8A8_MIN_M .. ops.W8A8_MAX_M: FP8 x FP8 on the FP8 matrix instruction (csrc/gemm_w8a8.hip)
+        if weight_quant not in (None, "fp8_block128", "fp8_block128_a8"):
+            raise ValueError(f"weight_quant {weight_quant!r}: None, 'fp8_block128' or 'fp8_block128_a8'")
+        if weight_quant == "fp8_block128_a8" and cfg.num_experts > 0:
+            raise ValueError("weight_quant='fp8_block128_a8' covers dense models only: the grouped expert GEMMs are W8A16 "
+                             "(use 'fp8_block128' for an expert model)")
         self.weight_quant = weight_quant
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self.fused = fused
@@ -238,6 +243,8 @@ class DenseDecoder:
             if weight_quant:  # layer by layer: the 16-bit originals of one layer at a time
                 for k in self.w8_names:
                     setattr(self.layers[-1], k, ops.quantize_fp8_block128(getattr(self.layers[-1], k)))
+                    if weight_quant == "fp8_block128_a8":
+                        getattr(self.layers[-1], k).act_quant = "fp8_group128"
         # gate_up rows in the block-32 interleaved order the fused projection + SiLU.mul epilogue needs (csrc/gemm_g3.hip);
         # every consumer goes through ops.linear_silu, the oracle gets the reference layout back (gate_up_reference)
         self.gate_up_ilv = bool(fused and _FUSE_SILU and device.type == "cuda" and self.inter % 64 == 0 and not self.moe
@@ -252,6 +259,8 @@ class DenseDecoder:
             ops.w8_reserve(device, max(getattr(self.layers[0], k).q.numel() for k in ("qkv", "o") + (() if self.moe else ("gate_up", "down"))))
             if self.moe:  # the tall route dequantises one layer's expert stacks
                 ops.moe_w8_reserve(device, cfg.num_experts, H, self.moe_inter)
+            if weight_quant == "fp8_block128_a8":  # the quantised activations of one projection input, decode batches;
+                ops.a8_reserve(device, ops.W8_MAX_M, max(H, self.q_dim, self.inter))  # the engine reserves its prefill chunk
         self.final_norm = ones(H)
         self.lm_head = self.embed if cfg.tie_word_embeddings else w(self.vocab_tp, H)
         self.cos_sin = fi.build_cos_sin_cache(D, cfg.max_position, cfg.rope_base, cfg.rope_scaling, device=device)

@@ -1097,9 +1097,12 @@ class Fp8Weight:
     """A projection weight as the FP8 checkpoints store it: `q` float8_e4m3fn [N, K] and `scales` fp32
     [N / 128, K / 128] (`weight_scale_inv`); the weight is q * scales per 128 x 128 block.  An expert stack has a leading
     dimension: q [E, N, K], scales [E, N / 128, K / 128] (viewed as [E N, K] it is a valid 2-D weight, N % 128 == 0)."""
-    __slots__ = ("q", "scales", "shape")
+    __slots__ = ("q", "scales", "shape", "act_quant")
 
-    def __init__(self, q: torch.Tensor, scales: torch.Tensor) -> None:
+    def __init__(self, q: torch.Tensor, scales: torch.Tensor, act_quant: Optional[str] = None) -> None:
+        if act_quant not in (None, "fp8_group128"):
+            raise ValueError(f"Fp8Weight: act_quant {act_quant!r}: None or 'fp8_group128'")
+        self.act_quant = act_quant  # "fp8_group128": batches of W8A8_MIN_M rows and more are served as W8A8 (w8a8_linear)
         if q.dim() not in (2, 3):
             raise ValueError(f"Fp8Weight: weight {tuple(q.shape)} must be [N, K] or [E, N, K]")
         N, K = q.shape[-2:]
@@ -1238,9 +1241,89 @@ def w8_tall_gemm(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = No
     return out
 
 
+# ---------------------------------------------------------------------------- W8A8 (csrc/gemm_w8a8.hip)
+# The batches at which ops.linear serves an Fp8Weight with act_quant == "fp8_group128" as W8A8.  The rule is the project's:
+# the batches at which quantiser + FP8-MFMA GEMM beat what ops.linear does today for an Fp8Weight by PLAN_MARGIN on ALL four
+# Qwen3-14B projections (tools/w8_bench.py --a8, profiles/w8a8_bench.json).  Measured at 64, 128, 256, 512 and
+# 2048 rows: only 256 qualifies (0.63 - 0.84 x today's time; 128: qkv 0.958, 512: qkv 0.973, 2048: 1.17 - 1.73 x slower than
+# dequantise + library), and nothing between the measured batches is claimed.
+W8A8_MIN_M = 256
+W8A8_MAX_M = 256
+_A8_SCRATCH: dict = {}
+
+
+def a8_reserve(device: torch.device, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(xq [M, K] e4m3, sx [M, K / 128] fp32) views of the per-device scratch w8a8_linear quantises into; reserved at load
+    time (model memory, nothing allocated under graph capture), grown here only if a larger batch shows up."""
+    key = torch.device(device).index or 0
+    need = M * K + 4 * M * (K // W8_BLOCK)
+    buf = _A8_SCRATCH.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _A8_SCRATCH[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf[: M * K].view(torch.float8_e4m3fn).view(M, K), buf[M * K: need].view(torch.float32).view(M, K // W8_BLOCK)
+
+
+def a8_quant(x: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(xq, sx) = msgl_a8_quant(x): x [M, K] bf16 -> e4m3 [M, K] and one fp32 scale per (row, 128-column group),
+    sx = max(amax, FLT_MIN) / 448, xq = e4m3(x / sx).  `out` = (xq, sx) to write into (xq may be a strided view)."""
+    _need_cuda(x)
+    M, K = x.shape
+    assert x.dim() == 2 and x.stride(1) == 1 and M >= 1, x.shape
+    xq, sx = out if out is not None else (torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device),
+                                          torch.empty((M, K // W8_BLOCK), dtype=torch.float32, device=x.device))
+    assert xq.shape == (M, K) and xq.stride(1) == 1 and xq.dtype == torch.float8_e4m3fn and xq.is_cuda
+    assert sx.shape == (M, K // W8_BLOCK) and sx.is_contiguous() and sx.dtype == torch.float32 and sx.is_cuda
+    check(lib().msgl_a8_quant(xq.data_ptr(), sx.data_ptr(), x.data_ptr(), M, K, x.stride(0), xq.stride(0), _dt(x), _stream()),
+          "a8_quant")
+    return xq, sx
+
+
+def w8a8_plan(M: int, N: int, K: int) -> Tuple[int, int]:
+    """(tm, k_slices) of msgl_w8a8_gemm_nt: a fixed function of the shape (no timing search, 256 CUs assumed on every
+    box).  tm = 256 rows of xq per workgroup above 128 rows (one workgroup per CU), else 128 (two per CU); k-slices fill
+    the machine when the tile grid is small: at least two 128-k blocks per slice, at most 16."""
+    tm = 256 if M > 128 else 128
+    tiles = (N // W8_BLOCK) * ((M + tm - 1) // tm)
+    target = _W8_CUS * (1 if tm == 256 else 2)
+    return tm, max(1, min(K // (2 * W8_BLOCK), 16, target // tiles))
+
+
+def w8a8_gemm(xq: torch.Tensor, sx: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None, tm: Optional[int] = None,
+              k_slices: Optional[int] = None) -> torch.Tensor:
+    """out[M, N] bf16 = sum over 128-k blocks of sx * w.scales * (xq @ w.q^T of the block), FP8 x FP8 (msgl_w8a8_gemm_nt)."""
+    _need_cuda(xq, sx, w.q, w.scales)
+    M, K = xq.shape
+    N = w.shape[0]
+    assert xq.dim() == 2 and w.q.dim() == 2 and K == w.shape[1] and xq.stride(1) == 1, (xq.shape, w.shape)
+    assert xq.dtype == torch.float8_e4m3fn and sx.dtype == torch.float32 and sx.shape == (M, K // W8_BLOCK) and sx.is_contiguous()
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=xq.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.is_cuda
+    plan = w8a8_plan(M, N, K)
+    ws = gemm_workspace(xq.device)
+    check(
+        lib().msgl_w8a8_gemm_nt(out.data_ptr(), xq.data_ptr(), sx.data_ptr(), w.q.data_ptr(), w.scales.data_ptr(), M, N, K,
+                                xq.stride(0), w.q.stride(0), out.stride(0), _dt(out), tm or plan[0], k_slices or plan[1],
+                                ws.data_ptr(), ws.numel(), _stream()),
+        "w8a8_gemm_nt",
+    )
+    return out
+
+
+def w8a8_linear(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Quantise x per (token, 128-column group) into the reserved scratch, then the FP8 x FP8 GEMM."""
+    if x.shape[0] == 0:
+        return x.new_empty((0, w.shape[0])) if out is None else out
+    _no_pending_slabs(x.device)
+    xq, sx = a8_quant(x, a8_reserve(x.device, x.shape[0], x.shape[1]))
+    return w8a8_gemm(xq, sx, w, out)
+
+
 def w8_linear(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     if x.shape[0] == 0:
         return x.new_empty((0, w.shape[0])) if out is None else out
+    if w.act_quant == "fp8_group128" and W8A8_MIN_M <= x.shape[0] <= W8A8_MAX_M:
+        return w8a8_linear(x, w, out)
     if x.shape[0] <= W8_TALL_MAX_M:
         _no_pending_slabs(x.device)
         return w8_gemm(x, w, out) if x.shape[0] < W8_TALL_MIN_M else w8_tall_gemm(x, w, out)
@@ -1252,7 +1335,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None)
     """out[M, N] = x[M, K] @ w[N, K]^T (the reference's `F.linear`, P/layers/linear.py:32): the hand-written
     weight-streaming kernel where skinny_tune() planned it (decode batches <= 64), else msgl_gemm_nt with the
     tuned library solution for the shape if gemm_tune() ran, else the library's heuristic.  An Fp8Weight goes to the
-    W8A16 kernel (M < W8_TALL_MIN_M), the tall-tile W8A16 kernel (up to W8_TALL_MAX_M) or through its bf16 scratch copy."""
+    W8A16 kernel (M < W8_TALL_MIN_M), the tall-tile W8A16 kernel (up to W8_TALL_MAX_M) or through its bf16 scratch copy;
+    with act_quant == "fp8_group128", batches of W8A8_MIN_M .. W8A8_MAX_M rows go to w8a8_linear (FP8 x FP8) instead."""
     if isinstance(w, Fp8Weight):
         return w8_linear(x, w, out)
     out, M, N, K = _gemm_args(x, w, out)

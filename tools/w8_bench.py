@@ -4,6 +4,10 @@ kernel existed (msgl_w8_gemm_nt up to 256 rows, msgl_w8_dequant + the 16-bit ops
 msgl_w8_tall_gemm_nt (csrc/gemm_w8_tall.hip) with ops.w8_tall_plan.
 
     python tools/w8_bench.py [--out profiles/w8_bench.json] [--layers 6] [--replays 24] [--rounds 9]
+    python tools/w8_bench.py --a8 [--out profiles/w8a8_bench.json] [--batches 64,128,256,512,2048]
+
+`--a8`: the W8A8 route (csrc/gemm_w8a8.hip) instead: columns `bf16`; `today` = what ops.linear does for an Fp8Weight without
+act_quant at that batch; `a8` = ops.w8a8_linear, the quantiser and the FP8-MFMA GEMM together (the model pays for both).
 
 Same process, same box, alternating: per (shape, M) the bf16 side first runs the project's plan search for the shape
 (model.tune_gemms' search: library solutions and the hand-written 16-bit kernels), then both sides are captured as
@@ -51,6 +55,26 @@ def capture(fn, weights, replays: int):
     return graph
 
 
+def a8_row(args, name, M, N, K, x, out, bf16, fp8, rep) -> dict:
+    graphs = {"bf16": capture(lambda w: ops.linear(x, w, out=out), bf16, args.replays),
+              "today": capture(lambda w: ops.linear(x, w, out=out), fp8, args.replays),
+              "a8": capture(lambda w: ops.w8a8_linear(x, w, out=out), fp8, args.replays)}
+    samples = {k: [] for k in graphs}
+    for _ in range(args.rounds):
+        for k, gr in graphs.items():
+            samples[k].append(replay_us(gr, args.replays))
+    us = {k: statistics.median(v) for k, v in samples.items()}
+    ref = x.float() @ fp8[(args.replays - 1) % args.layers].dequantize().t()
+    rel = ((out.float() - ref).abs().max() / ref.abs().max()).item()  # `out` holds the a8 graph's last call
+    return dict(name=name, M=M, N=N, K=K, bf16_us=round(us["bf16"], 2), today_us=round(us["today"], 2), a8_us=round(us["a8"], 2),
+                a8_over_today=round(us["a8"] / us["today"], 3), a8_over_bf16=round(us["a8"] / us["bf16"], 3),
+                a8_tflops=round(2.0 * M * N * K / (us["a8"] * 1e-6) / 1e12, 1),
+                today_route="w8_gemm" if M < ops.W8_TALL_MIN_M else "w8_tall" if M <= ops.W8_TALL_MAX_M else "dequant + linear",
+                a8_plan=list(ops.w8a8_plan(M, N, K)), bf16_kernel=rep["kernel"][:120],
+                spread_us={k: [round(min(v), 2), round(max(v), 2)] for k, v in samples.items()},
+                a8_max_rel_err_vs_unquantised_fp32=round(rel, 5))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / "w8_bench.json"))
@@ -58,6 +82,7 @@ def main() -> None:
     ap.add_argument("--layers", type=int, default=6)
     ap.add_argument("--replays", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--a8", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "w8_bench needs the GPU"
     dev = torch.device("cuda:0")
@@ -74,6 +99,10 @@ def main() -> None:
             x = torch.randn((M, K), generator=g, device=dev).bfloat16()
             out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
             rep = gemm_plan.tune_projection_gemms([(name, bf16, K)], [M], "heuristic", torch.bfloat16, dev)[0]
+            if args.a8:
+                rows.append(a8_row(args, name, M, N, K, x, out, bf16, fp8, rep))
+                print(json.dumps(rows[-1]), flush=True)
+                continue
             scratch = ops.w8_reserve(dev, N * K)[: N * K].view(N, K)
             old = (lambda w: ops.w8_gemm(x, w, out=out)) if M <= ops.W8_MAX_M else (
                 lambda w: ops.linear(x, ops.w8_dequant(w, scratch), out=out))
@@ -106,8 +135,9 @@ def main() -> None:
             print(json.dumps(rows[-1]), flush=True)
             del graphs
         del bf16, fp8
-    result = dict(model=cfg.name, device=torch.cuda.get_device_name(0), command="python tools/w8_bench.py",
-                  method=f"{args.replays} calls per captured graph over {args.layers} weight sets, the bf16, w8 and tall graphs "
+    result = dict(model=cfg.name, device=torch.cuda.get_device_name(0), command="python tools/w8_bench.py" + " --a8" * args.a8,
+                  method=f"{args.replays} calls per captured graph over {args.layers} weight sets, the "
+                         f"{'bf16, today and a8' if args.a8 else 'bf16, w8 and tall'} graphs "
                          f"replayed in turn, median of {args.rounds} replays each; bf16 = ops.linear after the project's plan "
                          f"search for the shape", rows=rows)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
