@@ -46,7 +46,7 @@ extern "C" {
 /* dtype codes for logits */
 #define MSGL_F32 2
 
-#define MSGL_ABI_VERSION 10
+#define MSGL_ABI_VERSION 11
 
 /* Last error message of the calling thread ("" if none). */
 const char* msgl_last_error(void);
@@ -258,6 +258,47 @@ int msgl_attn_prefill(void* out, const void* q, const void* k_cache, const void*
 /* Rows per q tile: tile_cu, total_tiles and tile_order of msgl_attn_prefill are in units of this many query rows
  * (MSGL_PREFILL_QTILE for both kernels). */
 int msgl_attn_prefill_q_tile(int impl);
+
+/* ------------------------------------------------------------------------
+ * FP8 (OCP e4m3fn) KV cache, csrc/attn_kv8.hip: what the mainstream servers call kv_cache_dtype = fp8_e4m3 with per-tensor
+ * k_scale / v_scale.  The pool holds ONE byte per element:
+ *   element = e4m3_rne(clamp(float(x) / scale, -448, 448)),   scale = k_scale (K) or v_scale (V), fp32, by value,
+ * x the bf16 value the 16-bit store would have written (for K: after qk-norm and RoPE, rounded to bf16), IEEE fp32
+ * division, bit-identical to (x.float() / scale).clamp(-448, 448).to(torch.float8_e4m3fn); the NaN encoding is never
+ * produced from finite input.  Attention computes
+ *   out = bf16(v_scale * sum_t p_t float(v8_t) / l),   p = softmax(sm_scale * k_scale * q . float(k8)),
+ * with q in bf16, e4m3 -> bf16 exact, bf16 MFMAs with fp32 accumulation, P rounded to bf16 before P.V; k_scale is folded
+ * into the exponent's scale, v_scale into the final normalisation (split-KV: into the partial sums).  Deterministic, no
+ * atomics, nothing allocated or synchronised, capturable, grids are functions of the arguments only.
+ *
+ * The three entry points take the arguments of msgl_qk_norm_rope_store / msgl_attn_decode / msgl_attn_prefill plus the two
+ * scales; k_cache / v_cache are e4m3 bytes and cache_stride / kv_stride_tok / kv_stride_head are in bytes = elements.
+ *   msgl_qk_norm_rope_store_kv8  q and k are normalised and rotated in place in bf16 (the same bits as the 16-bit entry
+ *                                point); only the scatter to the pool quantises.  No slab-input form.
+ *   msgl_attn_decode_kv8         plan (msgl_attn_decode_plan) and workspace layout are the 16-bit ones; both page-table
+ *                                forms (slot_run >= 16 / token-granular), any GQA group 1 .. 16; select code 0 (or 71) only.
+ *   msgl_attn_prefill_kv8        128-row q tiles; tile_cu / total_tiles / tile_order as msgl_attn_prefill; impl 0 / 4 only.
+ * All three return MSGL_EINVAL with a message, before any launch, for head_dim != 128, dtype != MSGL_BF16, a non-finite
+ * or non-positive scale, null pointers, and cache pointers or cache strides that are not multiples of 16 bytes.
+ * ---------------------------------------------------------------------- */
+int msgl_qk_norm_rope_store_kv8(void* q, void* k, const void* v, const void* q_norm_w, const void* k_norm_w, float eps,
+                                const void* positions, int positions_is_i64, const float* cos_sin_cache, void* k_cache,
+                                void* v_cache, const void* out_loc, int out_loc_is_i64, int64_t num_tokens,
+                                int num_q_heads, int num_k_heads, int head_dim, int64_t q_stride, int64_t k_stride,
+                                int64_t v_stride, int64_t cache_stride, int dtype, float k_scale, float v_scale,
+                                void* stream);
+int msgl_attn_decode_kv8(void* out, const void* q, const void* k_cache, const void* v_cache, const int32_t* page_table,
+                         int64_t pt_stride, const int32_t* req_rows, const int32_t* seq_lens, const int32_t* plan,
+                         void* workspace, int batch, int max_bs, int capacity, int num_q_heads, int num_kv_heads,
+                         int head_dim, int64_t q_stride_tok, int64_t kv_stride_tok, int64_t kv_stride_head,
+                         int64_t out_stride_tok, float sm_scale, int slot_run, int dtype, float k_scale, float v_scale,
+                         void* stream);
+int msgl_attn_prefill_kv8(void* out, const void* q, const void* k_cache, const void* v_cache, const int32_t* page_table,
+                          int64_t pt_stride, const int32_t* req_rows, const int32_t* seq_lens,
+                          const int32_t* cu_seqlens_q, const int32_t* tile_cu, int batch, int total_tiles,
+                          int num_q_heads, int num_kv_heads, int head_dim, int64_t q_stride_tok, int64_t kv_stride_tok,
+                          int64_t kv_stride_head, int64_t out_stride_tok, float sm_scale, int dtype,
+                          const int32_t* tile_order, int impl, float k_scale, float v_scale, void* stream);
 
 /* ------------------------------------------------------------------------
  * Sampling.  Replaces torch.argmax at P/engine/sample.py:73-74 and

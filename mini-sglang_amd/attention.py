@@ -125,16 +125,18 @@ class HipAttnBackend:
         out = torch.empty((q.shape[0], self.qo_heads, self.head_dim), dtype=q.dtype, device=q.device)
         k_tok, v_tok = self._kv_tokens(layer_id)
         table = self.ctx.page_table
+        # an FP8 pool (kvcache.MHAKVCache with an e4m3 dtype) carries its per-tensor scales; ops routes on the pool's dtype
+        scales = dict(k_scale=getattr(self.kvcache, "k_scale", 1.0), v_scale=getattr(self.kvcache, "v_scale", 1.0))
         if md.max_seqlen_q == 1:
             if md.plan is None:  # prepared for replay but run eagerly by the host: plan on first use
                 md.plan = torch.empty(self._plan_words, dtype=torch.int32, device=self.device)
                 ops.attn_decode_plan(md.plan, md.seq_lens, md.batch, self.max_bs, self.capacity, self.qo_heads,
                                      self.kv_heads)
             ops.attn_decode(out, q, k_tok, v_tok, table, md.req_rows, md.seq_lens, md.plan, self._workspace,
-                            md.batch, self.max_bs, self.capacity, self.scale, slot_run=self.slot_run)
+                            md.batch, self.max_bs, self.capacity, self.scale, slot_run=self.slot_run, **scales)
         else:
             ops.attn_prefill(out, q, k_tok, v_tok, table, md.req_rows, md.seq_lens, md.cu_seqlens_q, md.tile_cu,
-                             md.batch, md.total_tiles, self.scale, tile_order=md.tile_order)
+                             md.batch, md.total_tiles, self.scale, tile_order=md.tile_order, **scales)
         return out
 
     # ------------------------------------------------------------------ metadata

@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "attn_decode.hip",
     "attn_prefill.hip",
     "attn_d64.hip",
+    "attn_kv8.hip",
     "sampling.hip",
     "gemm_skinny.hip",
     "gemm_rowstream.hip",

@@ -1195,6 +1195,14 @@ static int heads_per_unit(int group) {
   return 1;
 }
 
+int decode_select_code() { return decode_impl(); }
+
+int64_t decode_plan_waves(int num_q_heads, int num_kv_heads, int capacity, int max_bs, int* heads_per_wave) {
+  const int G = heads_per_unit(num_q_heads / num_kv_heads);
+  *heads_per_wave = G;
+  return (int64_t)decode_target_slots(G, num_q_heads / G, capacity, max_bs) * (num_q_heads / G);
+}
+
 }  // namespace msgl
 
 using namespace msgl;

@@ -120,4 +120,10 @@ __device__ __forceinline__ TileRequest find_request(const PrefillParams& p, int 
 int launch_decode_d64(const DecodeParams& p, int batch, int64_t waves, int dtype, hipStream_t stream);
 int launch_prefill_d64(const PrefillParams& p, int total_tiles, int dtype, hipStream_t stream);
 
+// What the FP8-cache decode entry point (csrc/attn_kv8.hip) needs of attn_decode.hip: the running msgl_attn_decode_select
+// code, and the wave count msgl_attn_decode_plan sizes the slots for with these head counts (*heads_per_wave = q heads
+// packed per work unit), so that its grid covers every slot of a plan made by the unchanged plan kernel.
+int decode_select_code();
+int64_t decode_plan_waves(int num_q_heads, int num_kv_heads, int capacity, int max_bs, int* heads_per_wave);
+
 }  // namespace msgl

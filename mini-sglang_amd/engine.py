@@ -126,11 +126,31 @@ class EngineConfig:
     # "fp8_block128": qkv / o and gate_up / down or the experts as block-scaled e4m3; "fp8_block128_a8": dense models, the
     # projections' activations as e4m3 per (token, 128 columns) as well (model.DenseDecoder)
     weight_quant: Optional[str] = None
+    # "fp8_e4m3": the KV pool holds e4m3 bytes with per-tensor scales 1.0 (csrc/attn_kv8.hip): half the bytes per page and
+    # per decode step.  head_dim 128, bf16, the fused qkv path; composes with every weight_quant and with MoE models
+    kv_quant: Optional[str] = None
     seed: int = 42
 
     @property
     def max_seq_len(self) -> int:
         return self.max_seq_len_override or self.model.max_position
+
+    @property
+    def kv_dtype(self) -> torch.dtype:
+        """Element type of the KV pool."""
+        return self.dtype if self.kv_quant is None else torch.float8_e4m3fn
+
+    def __post_init__(self) -> None:  # an unservable kv_quant is refused here, before anything is allocated
+        if self.kv_quant is None:
+            return
+        if self.kv_quant != "fp8_e4m3":
+            raise ValueError(f"kv_quant {self.kv_quant!r}: None or 'fp8_e4m3'")
+        if self.model.head_dim != 128:
+            raise ValueError(f"kv_quant='fp8_e4m3' needs head_dim 128, not {self.model.head_dim}")
+        if self.dtype != torch.bfloat16:
+            raise ValueError(f"kv_quant='fp8_e4m3' needs bf16 activations, not {self.dtype}")
+        if not self.fused_qkv_path:
+            raise ValueError("kv_quant='fp8_e4m3' needs fused_qkv_path=True: only the fused store quantises")
 
 
 class ForwardOutput(NamedTuple):
@@ -147,7 +167,7 @@ def determine_num_pages(free_before: int, free_after: int, cfg: EngineConfig) ->
     """P/engine/engine.py:148-168: (memory_ratio * free_before - model_bytes) // bytes_per_page."""
     m = cfg.model
     cache_per_page = (2 * m.head_dim * heads_per_rank(m.num_kv_heads, cfg.tp_size, replicate=True) * cfg.page_size
-                      * torch.empty((), dtype=cfg.dtype).element_size() * m.num_layers)
+                      * torch.empty((), dtype=cfg.kv_dtype).element_size() * m.num_layers)
     if cfg.num_page_override is not None:
         return cfg.num_page_override
     model_memory = free_before - free_after
@@ -285,7 +305,7 @@ class Engine:
         self.num_pages = determine_num_pages(free_before, free_after, cfg)
         num_tokens = self.num_pages * cfg.page_size
         self.ctx.kv_cache = self.kv_cache = create_kvcache_pool(
-            cfg.model, self.num_pages + 1, cfg.page_size, cfg.dtype, self.device, tp_size=cfg.tp_size)  # +1 dummy
+            cfg.model, self.num_pages + 1, cfg.page_size, cfg.kv_dtype, self.device, tp_size=cfg.tp_size)  # +1 dummy
         self.max_seq_len = min(cfg.max_seq_len, num_tokens)
         self.aligned_max_seq_len = _align_up_32(self.max_seq_len)
         self.ctx.page_table = self.page_table = torch.zeros(

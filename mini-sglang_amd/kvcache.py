@@ -30,8 +30,12 @@ def heads_per_rank(total: int, ranks: int, replicate: bool = False) -> int:
 
 class MHAKVCache:
     def __init__(self, num_kv_heads: int, num_layers: int, head_dim: int, num_pages: int, page_size: int,
-                 dtype: torch.dtype, device: torch.device, tp_size: int = 1) -> None:
+                 dtype: torch.dtype, device: torch.device, tp_size: int = 1, k_scale: float = 1.0,
+                 v_scale: float = 1.0) -> None:
+        """dtype torch.float8_e4m3fn: one byte per element, element = e4m3(x / k_scale) (K) or e4m3(x / v_scale) (V), one
+        fp32 scale per tensor (csrc/attn_kv8.hip); written by ops.qk_norm_rope_store, read by ops.attn_decode / attn_prefill."""
         heads = heads_per_rank(num_kv_heads, tp_size, replicate=True)
+        self.k_scale, self.v_scale = float(k_scale), float(v_scale)
         slots = num_pages * page_size
         self.pool = torch.empty((2, num_layers, num_pages, page_size, heads, head_dim), device=device, dtype=dtype)
         self._layers = num_layers
@@ -59,6 +63,9 @@ class MHAKVCache:
         return self.pool[1, index].view(self._tok_shape)
 
     def store_kv(self, k: torch.Tensor, v: torch.Tensor, out_loc: torch.Tensor, layer_id: int) -> None:
+        if self.pool.dtype == torch.float8_e4m3fn:
+            raise RuntimeError("store_kv copies bytes and cannot quantise: an FP8 KV pool is written by the fused path "
+                               "(ops.qk_norm_rope_store), which the engine takes with fused_qkv_path=True")
         ops.store_kv(self.k_rows(layer_id), self.v_rows(layer_id), out_loc,
                      k.view(k.shape[0], -1), v.view(v.shape[0], -1))
 
@@ -76,8 +83,8 @@ class MHAKVCache:
 
 
 def create_kvcache_pool(model_config, num_pages: int, page_size: int, dtype: torch.dtype, device: torch.device,
-                        tp_size: int = 1) -> MHAKVCache:
+                        tp_size: int = 1, k_scale: float = 1.0, v_scale: float = 1.0) -> MHAKVCache:
     """P/kvcache/__init__.py:27-44."""
     return MHAKVCache(num_kv_heads=model_config.num_kv_heads, num_pages=num_pages, page_size=page_size,
                       num_layers=model_config.num_layers, head_dim=model_config.head_dim, device=device,
-                      dtype=dtype, tp_size=tp_size)
+                      dtype=dtype, tp_size=tp_size, k_scale=k_scale, v_scale=v_scale)

@@ -461,6 +461,8 @@ class DenseDecoder:
         dtype) when given -- the graph runner's static buffer."""
         cfg, D = self.cfg, self.cfg.head_dim
         backend, kv = ctx.attn_backend, ctx.kv_cache
+        kv8 = kv.dtype == torch.float8_e4m3fn  # FP8 pool: ops.linear for qkv, then the quantising store (no slab form)
+        kv_scales = dict(k_scale=kv.k_scale, v_scale=kv.v_scale) if kv8 else {}
         x = ops.embedding_gather(self.embed, batch.input_ids,
                                  vocab_range=self.vocab_range if self.tp_size > 1 else None)
         x = self.comm.all_reduce(x)
@@ -499,7 +501,7 @@ class DenseDecoder:
                 pending = None
             else:
                 # a k-sliced full-batch plan leaves the qkv projection's reduce to the fused norm / RoPE / store pass
-                qkv, slabs = ops.linear_slabs(x, lw.qkv) if self.fused and _SLAB_NORM else (ops.linear(x, lw.qkv), None)
+                qkv, slabs = ops.linear_slabs(x, lw.qkv) if self.fused and _SLAB_NORM and not kv8 else (ops.linear(x, lw.qkv), None)
             q, k, v = qkv.split([self.q_dim, self.kv_dim, self.kv_dim], dim=-1)
             if self.fused:
                 kc, vc = kv.k_cache(li), kv.v_cache(li)
@@ -510,7 +512,7 @@ class DenseDecoder:
                 else:
                     ops.qk_norm_rope_store(q, k, v, lw.q_norm, lw.k_norm, cfg.rms_norm_eps, batch.positions,
                                            self.cos_sin, kc.view(-1, self.kv_dim), vc.view(-1, self.kv_dim),
-                                           batch.out_loc, D)
+                                           batch.out_loc, D, **kv_scales)
                 o = backend.attend(q.view(-1, self.hq, D), li, batch)
             else:  # P/layers/attention.py:47-57
                 if lw.q_norm is not None:

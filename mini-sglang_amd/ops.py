@@ -209,15 +209,40 @@ def rope_neox_inplace(positions: torch.Tensor, query: torch.Tensor, key: torch.T
     )
 
 
+def _is_kv8(k_cache: torch.Tensor, k_scale: float, v_scale: float) -> bool:
+    """True for an FP8 (e4m3) KV pool, which csrc/attn_kv8.hip serves; a 16-bit pool has no scales to apply."""
+    if k_cache.dtype == torch.float8_e4m3fn:
+        return True
+    if k_scale != 1.0 or v_scale != 1.0:
+        raise ValueError(f"k_scale / v_scale belong to an FP8 KV cache, not to a {k_cache.dtype} one")
+    return False
+
+
 def qk_norm_rope_store(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_norm_w: Optional[torch.Tensor],
                        k_norm_w: Optional[torch.Tensor], eps: float, positions: torch.Tensor,
                        cos_sin_cache: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                       out_loc: torch.Tensor, head_dim: int) -> None:
-    """Fused qk-norm -> RoPE -> KV store over [T, H*D] row views q, k, v (see msgl_hip.h)."""
+                       out_loc: torch.Tensor, head_dim: int, k_scale: float = 1.0, v_scale: float = 1.0) -> None:
+    """Fused qk-norm -> RoPE -> KV store over [T, H*D] row views q, k, v (see msgl_hip.h).  An e4m3 pool
+    (k_cache.dtype == torch.float8_e4m3fn) receives e4m3(k / k_scale), e4m3(v / v_scale): msgl_qk_norm_rope_store_kv8."""
     _need_cuda(q, k, v, positions, cos_sin_cache, k_cache, v_cache, out_loc)
     assert q.dim() == 2 and k.dim() == 2 and v.dim() == 2 and k_cache.dim() == 2 and v_cache.dim() == 2
     assert k.shape[1] == v.shape[1] == k_cache.shape[1] == v_cache.shape[1]
-    assert k_cache.stride(0) == v_cache.stride(0)
+    assert k_cache.stride(0) == v_cache.stride(0) and k_cache.dtype == v_cache.dtype
+    if _is_kv8(k_cache, k_scale, v_scale):
+        assert k_cache.stride(1) == v_cache.stride(1) == 1
+        check(
+            lib().msgl_qk_norm_rope_store_kv8(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                q_norm_w.data_ptr() if q_norm_w is not None else None,
+                k_norm_w.data_ptr() if k_norm_w is not None else None, float(eps), positions.data_ptr(),
+                _is_i64(positions), cos_sin_cache.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                out_loc.data_ptr(), _is_i64(out_loc), q.shape[0], q.shape[1] // head_dim, k.shape[1] // head_dim,
+                head_dim, q.stride(0), k.stride(0), v.stride(0), k_cache.stride(0), _dt(q), float(k_scale),
+                float(v_scale), _stream(),
+            ),
+            "qk_norm_rope_store_kv8",
+        )
+        return
     check(
         lib().msgl_qk_norm_rope_store(
             q.data_ptr(), k.data_ptr(), v.data_ptr(),
@@ -330,9 +355,10 @@ def attn_decode_plan(plan: torch.Tensor, seq_lens: torch.Tensor, batch: int, max
 def attn_decode(out: torch.Tensor, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                 page_table: torch.Tensor, req_rows: Optional[torch.Tensor], seq_lens: torch.Tensor,
                 plan: torch.Tensor, workspace: torch.Tensor, batch: int, max_bs: int, capacity: int,
-                sm_scale: float, slot_run: int = 1) -> None:
+                sm_scale: float, slot_run: int = 1, k_scale: float = 1.0, v_scale: float = 1.0) -> None:
     """q: [B, Hq, D] (token stride free), k_cache/v_cache: [slots, Hkv, D], out: [B, Hq, D].
-    slot_run: aligned runs of this many positions map to consecutive slots (the engine's page_size)."""
+    slot_run: aligned runs of this many positions map to consecutive slots (the engine's page_size).
+    An e4m3 cache (torch.float8_e4m3fn, values = e4m3(x / scale)) goes to msgl_attn_decode_kv8 with q / out in bf16."""
     _need_cuda(out, q, k_cache, v_cache, page_table, seq_lens, plan, workspace)
     assert q.dim() == 3 and k_cache.dim() == 3 and out.dim() == 3
     hq, d = q.shape[1], q.shape[2]
@@ -340,6 +366,19 @@ def attn_decode(out: torch.Tensor, q: torch.Tensor, k_cache: torch.Tensor, v_cac
     assert q.stride(2) == 1 and q.stride(1) == d and out.stride(2) == 1 and out.stride(1) == d
     assert k_cache.stride(2) == 1 and v_cache.stride() == k_cache.stride() and v_cache.shape == k_cache.shape
     assert page_table.dtype == torch.int32 and page_table.dim() == 2 and page_table.stride(1) == 1
+    if _is_kv8(k_cache, k_scale, v_scale):
+        assert q.dtype == out.dtype and k_cache.dtype == v_cache.dtype
+        check(
+            lib().msgl_attn_decode_kv8(
+                out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), page_table.data_ptr(),
+                page_table.stride(0), req_rows.data_ptr() if req_rows is not None else None, seq_lens.data_ptr(),
+                plan.data_ptr(), workspace.data_ptr(), batch, max_bs, capacity, hq, hkv, d, q.stride(0),
+                k_cache.stride(0), k_cache.stride(1), out.stride(0), float(sm_scale), int(slot_run), _dt(q),
+                float(k_scale), float(v_scale), _stream(),
+            ),
+            "attn_decode_kv8",
+        )
+        return
     assert q.dtype == k_cache.dtype == v_cache.dtype == out.dtype
     check(
         lib().msgl_attn_decode(
@@ -372,7 +411,8 @@ def prefill_q_tile(impl: Optional[int] = None) -> int:
 def attn_prefill(out: torch.Tensor, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  page_table: torch.Tensor, req_rows: Optional[torch.Tensor], seq_lens: torch.Tensor,
                  cu_seqlens_q: torch.Tensor, tile_cu: torch.Tensor, batch: int, total_tiles: int,
-                 sm_scale: float, tile_order: Optional[torch.Tensor] = None, impl: Optional[int] = None) -> None:
+                 sm_scale: float, tile_order: Optional[torch.Tensor] = None, impl: Optional[int] = None,
+                 k_scale: float = 1.0, v_scale: float = 1.0) -> None:
     """tile_order: optional int32 [total_tiles] schedule of the q tiles (heaviest first); impl: None = process default
     (PREFILL_IMPL), 0 = 4 the DMA-staged kernel, 2 its register-staged predecessor (include/msgl_hip.h; anything else is
     refused by the library).  tile_cu / total_tiles / tile_order are in units of prefill_q_tile(impl) query rows."""
@@ -387,6 +427,20 @@ def attn_prefill(out: torch.Tensor, q: torch.Tensor, k_cache: torch.Tensor, v_ca
     assert q.stride(2) == 1 and q.stride(1) == d and out.stride(2) == 1 and out.stride(1) == d
     assert k_cache.stride(2) == 1 and v_cache.stride() == k_cache.stride()
     assert page_table.dtype == torch.int32 and page_table.stride(1) == 1
+    if _is_kv8(k_cache, k_scale, v_scale):  # an e4m3 cache: msgl_attn_prefill_kv8, q / out in bf16
+        assert q.dtype == out.dtype and k_cache.dtype == v_cache.dtype
+        check(
+            lib().msgl_attn_prefill_kv8(
+                out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), page_table.data_ptr(),
+                page_table.stride(0), req_rows.data_ptr() if req_rows is not None else None, seq_lens.data_ptr(),
+                cu_seqlens_q.data_ptr(), tile_cu.data_ptr(), batch, total_tiles, hq, hkv, d, q.stride(0),
+                k_cache.stride(0), k_cache.stride(1), out.stride(0), float(sm_scale), _dt(q),
+                tile_order.data_ptr() if tile_order is not None else None, int(impl), float(k_scale), float(v_scale),
+                _stream(),
+            ),
+            "attn_prefill_kv8",
+        )
+        return
     check(
         lib().msgl_attn_prefill(
             out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), page_table.data_ptr(),
